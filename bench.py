@@ -3,13 +3,21 @@ step (fwd + bwd + [RCCL all-reduce] + clip + AdamW(amsgrad) + schedule) on
 MI355X, bf16 MFMA / fp32 masters, B=64 per GPU, 224x224 images, 32-token
 questions (BASELINE.json configs[1]; configs[2] when launched on 8 GPUs).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N ... bench.py --gpus N     (one process per GPU)
 
 Synthetic data (no datasets offline): a pool of 4 batches per rank is made
 resident in HBM before timing; each timed step copies one into the static input
 buffers (device to device) and replays the captured step graph.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's
+results if `--dump-outputs DIR` is given (dump_outputs) and prints the line.  `--full`
+adds the legs that take runs of their own: the per-kernel rooflines (`roofline_hbm`,
+`roofline_gemm`, `sga_mfma`, `roofline_fp8`), the same workload through the N > 1 code
+path at world 1 (`dp_world1`), the DataParallelStep collective timing (`dp`) and the CPU
+oracle baseline (`cpu_baseline`); `--no-kernel-rooflines`, `--no-dp-line` and
+`--no-cpu-baseline` drop single legs of a `--full` run.
 
 `--gpus N` with N > 1 and no torchrun environment: this process starts N ranks
 itself (one child process per GPU, before anything touches the GPU), waits for
@@ -282,7 +290,9 @@ def bench_vit(args, pkg, dev):
                         "frac": round(tf / MFMA_PEAK_TFLOPS, 4), "traffic": None,
                         "flop_per_step": fpp * B, "step_gpu_ms": round(gpu_step * 1e3, 4)},
            "loss": round(float(eng.LOSS.item()), 5), "grad_norm": round(eng.last_grad_norm(), 4)}
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng)
+    if args.full and not args.no_cpu_baseline:
         from oracle import vit_oracle as orc
         cb, steps, warm = 16, 3, 1
         tr = orc.VitOracleTrainer(vm.make_state_dict(seed=0), warmup=10, total=1000, dropout=0.1)
@@ -308,6 +318,37 @@ def emit(out):
     f = _OUT or sys.stdout
     f.write(json.dumps(out) + "\n")
     f.flush()
+
+
+DUMP_PARAMS = 1 << 20          # updated parameters written by --dump-outputs (a fixed sample of the arena)
+
+
+def dump_outputs(d, eng):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy (fp32):
+    log_probs [B, answers] and loss [1] (what trainer.train_one_step returns), grad_norm [1] (the
+    step's clip norm) and params_sample, DUMP_PARAMS entries of the updated fp32 parameter arena
+    at indices drawn once from a fixed seed (the whole arena is 0.57 GB). The batches, the initial
+    weights and the dropout seed are fixed by the arguments, so two builds run with the same
+    arguments dump the same step.
+    The last step's AdamW update is deferred (it is still pending in the engine), so it is
+    applied here to read the parameters, and the optimizer state it writes (parameters, moments,
+    bf16 shadow, the pending flag) is then put back: the engine is left exactly as the timed
+    steps left it, and the `--full` legs after the dump (the AdamW pass of `roofline_hbm` returns
+    at once unless an update is pending) measure what they measure without a dump."""
+    state = [t for t in (getattr(eng, k, None) for k in ("P32", "M", "V", "VMAX", "P16", "opt_state"))
+             if isinstance(t, torch.Tensor)]
+    saved = [t.clone() for t in state]
+    eng.flush_optimizer()                               # the deferred AdamW update of the last step
+    n = eng.P32.numel()
+    idx = np.sort(np.random.default_rng(0).integers(0, n, size=min(n, DUMP_PARAMS)))
+    arrays = {"log_probs": eng.LOGP, "loss": eng.LOSS, "grad_norm": torch.tensor([eng.last_grad_norm()]),
+              "params_sample": eng.P32[torch.as_tensor(idx, device=eng.P32.device)]}
+    for t, s in zip(state, saved):
+        t.copy_(s)
+    del saved
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def spawn_ranks(n):
@@ -488,9 +529,15 @@ def main():
     ap.add_argument("--config5", action="store_true",
                     help="BASELINE configs[4]: ResNet50 + T5-large + 6xSGA at width 1024, 384x384 images, fp8 (e4m3) "
                          "forward weight GEMMs (per GPU; DP over N GPUs as for config 2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: per-kernel rooflines, "
+                         "the world-1 DataParallelStep line, the DP collective timing, the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results to DIR/<name>.npy (bench.dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-kernel-rooflines", action="store_true", help="skip the per-kernel replays after the timed region")
+    ap.add_argument("--no-kernel-rooflines", action="store_true",
+                    help="--full: skip the per-kernel replays after the timed region")
     ap.add_argument("--shard-optimizer", action="store_true",
                     help="N > 1: reduce-scatter + sharded AdamW + all-gather instead of the bucketed all-reduce")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -520,7 +567,7 @@ def main():
     ap.add_argument("--main-stream", choices=("default", "side"), default="default",
                     help="experiment: issue the step on torch's default stream or on a stream of its own")
     ap.add_argument("--no-dp-line", action="store_true",
-                    help="N = 1: skip the second timing of the same workload through the N > 1 code path "
+                    help="--full, N = 1: skip the second timing of the same workload through the N > 1 code path "
                          "(dp.DataParallelStep over a world-1 RCCL group; JSON key dp_world1)")
     ap.add_argument("--rehearse", action="store_true",
                     help="run every rank on cuda:0 over gloo: exercises the N-rank code path (bucketing, "
@@ -580,6 +627,8 @@ def main():
     dt, gpu_step, t_issue = time_steps(args, step, dev, dist)
     loss = float(eng.LOSS.item())
     gnorm = eng.last_grad_norm()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng)
     pairs = world * B * args.steps
     value = pairs / dt
     survey_cfg = (args.image_size, args.seq_len, NB) == (224, 32, 3) and not args.config5
@@ -661,7 +710,7 @@ def main():
         "loss": round(loss, 5), "grad_norm": round(gnorm, 4),
         "host_issue_ms_per_step": round(t_issue * 1e3 / args.steps, 3),
     }
-    if use_dp:                             # collective completion + exposed wait (HIP events), on 3
+    if use_dp and args.full:               # collective completion + exposed wait (HIP events), on 3
         dps.timing = True                  # steps after the timed region (its waits would perturb it)
         for i in range(3):
             step(args.steps + i)
@@ -674,15 +723,15 @@ def main():
         ps = [torch.empty_like(p) for _ in range(world)]
         dist.all_gather(ps, p)
         out["rehearsal_lockstep"] = all(torch.equal(q, ps[0]) for q in ps)
-    elif not args.no_kernel_rooflines:
+    elif args.full and not args.no_kernel_rooflines:
         out.update(kernel_rooflines(eng, torch.cuda.current_stream(dev), pmc))   # PMC: the committed shapes only
-    if world == 1 and not use_dp and not args.no_dp_line and not args.no_graph:
+    if args.full and world == 1 and not use_dp and not args.no_dp_line and not args.no_graph:
         # the N > 1 code path at N = 1, a second line beside the headline (same workload, same timing)
         del eng, dps, step
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
         out["dp_world1"] = dp_world1_line(args, pkg, dev, pool, lm, dt)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(pkg)
     if rank == 0:
         emit(out)

@@ -1,5 +1,6 @@
 """bench.py's host-side helpers (no GPU): the algorithmic byte model behind `roofline.alg_bytes`
- and the CU-mask parser of the `--res-cumask` experiment."""
+(VERDICT r04 item 5), the CU-mask parser of the `--res-cumask` experiment and the files
+`--dump-outputs` writes."""
 import os
 import sys
 
@@ -68,3 +69,54 @@ def test_byte_model_of_argument_calls():
     for touched in (0, 256):
         assert bench.call_bytes(C("vqa_adamw_rows", 0, 0, rows, cols, touched, 0, 0)) == \
             rows * 4 + (rows - t) * cols * 34
+
+
+def test_dump_outputs_writes_the_step_results(tmp_path):
+    """--dump-outputs: fp32 .npy files of the step's log-probs, loss, clip norm and a parameter
+    sample at the same seeded indices on every call, read after the pending AdamW update is
+    applied -- and the engine is left as it was found: the parameters, moments, bf16 shadow and
+    the pending flag are put back, so the `--full` legs that run after the dump (the AdamW pass
+    of roofline_hbm returns at once unless an update is pending) see what the timed steps left."""
+    import types
+
+    import numpy as np
+    import torch
+    PENDING = 8                                    # lib.ST_PENDING
+    n = 3 * bench.DUMP_PARAMS + 7
+    eng = types.SimpleNamespace(LOGP=torch.arange(8 * 170, dtype=torch.float32).reshape(8, 170),
+                                LOSS=torch.tensor([1.5]), P32=torch.arange(n, dtype=torch.float32),
+                                M=torch.zeros(n), V=torch.zeros(n), VMAX=torch.zeros(n),
+                                P16=torch.arange(n, dtype=torch.float32).to(torch.bfloat16),
+                                opt_state=torch.zeros(16), last_grad_norm=lambda: 2.25)
+    eng.opt_state[PENDING] = 1.0
+    flushed = []
+
+    def flush():                                   # the deferred update, as the engine applies it
+        assert eng.opt_state[PENDING] == 1.0, "the update must still be pending at every dump"
+        flushed.append(1)
+        eng.P32 += 0.5
+        eng.M += 1.0
+        eng.V += 2.0
+        eng.VMAX += 2.0
+        eng.P16.copy_(eng.P32)
+        eng.opt_state[PENDING] = 0.0
+    eng.flush_optimizer = flush
+    before = {k: getattr(eng, k).clone() for k in ("P32", "M", "V", "VMAX", "P16", "opt_state")}
+    ptrs = {k: getattr(eng, k).data_ptr() for k in before}
+    bench.dump_outputs(str(tmp_path / "a"), eng)
+    bench.dump_outputs(str(tmp_path / "b"), eng)
+    assert len(flushed) == 2
+    for k, t in before.items():                    # same buffers (prepared calls hold their addresses), same contents
+        assert getattr(eng, k).data_ptr() == ptrs[k] and torch.equal(getattr(eng, k), t), k
+    assert eng.opt_state[PENDING] == 1.0
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["grad_norm.npy", "log_probs.npy", "loss.npy", "params_sample.npy"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    np.testing.assert_array_equal(got["log_probs.npy"], eng.LOGP.numpy())
+    assert got["loss.npy"].tolist() == [1.5] and got["grad_norm.npy"].tolist() == [2.25]
+    s = got["params_sample.npy"]
+    assert s.shape == (bench.DUMP_PARAMS,) and np.all(np.diff(s) >= 0) and s[-1] > 2 * bench.DUMP_PARAMS
+    assert np.all(s % 1.0 == 0.5), "the sample holds the updated parameters"
+    for f, a in got.items():
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f), a)
