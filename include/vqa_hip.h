@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VQA_ABI_VERSION 18
+#define VQA_ABI_VERSION 19
 #define VQA_OK 0
 #define VQA_ERR_INVALID 1000
 
@@ -133,6 +133,36 @@ typedef struct vqa_gemm_desc {
   const float* scale_a;
   const float* scale_b;
   long long stride_scale_a, stride_scale_b;
+  /* norm != 0: GEMM, then normalise the rows it produced, in ONE launch.  The epilogue runs
+   * as usual (alpha*acc + bias, branch dropout, residual -> c32); the workgroup that finishes
+   * last of a row block's column tiles reads the block's c32 rows back and writes exactly what
+   * vqa_layernorm_fwd (norm = 1: y32 and/or y16, mean, rstd) or vqa_rmsnorm_fwd (norm = 2: y32
+   * and/or y16, optional rstd, optional norm_drop on y at element row*n + col) would write for
+   * that c32 -- the same bits.  norm_w = gamma / the RMS weight, norm_b = beta (LayerNorm only).
+   * batch z uses norm_w / norm_b + z*stride_norm_w, the y outputs + z*stride_norm_y and
+   * mean / rstd + z*stride_norm_stat; the strides are signed (an output stack may be written
+   * last batch first).
+   * Needs: c32 with ldc32 == n, n % 256 == 0, n <= 1024, beta == 0, relu == 0, k-contiguous A
+   * and B (a_trans = b_trans = 0) with no a_conv / b_conv, splitk <= 1, no mask16, the
+   * vectorised epilogue (n, ld*, strides multiples of 8, 16-byte aligned pointers), norm_w /
+   * norm_b / norm_y32 16-byte and norm_y16 8-byte aligned with strides multiples of 4,
+   * config 0 or one of 3, 4, 5, 6, 7, 21, and batch * ceil(m / BM) <= 16384 (BM = the rows
+   * of the tile config that runs, vqa_gemm_select).
+   * LayerNorm: norm_b, norm_mean, norm_rstd required, no norm_drop.  RMSNorm: norm_b and
+   * norm_mean NULL; norm_drop needs batch 1.  Anything else is VQA_ERR_INVALID, nothing written.
+   * workspace: >= vqa_gemm_workspace_bytes(d) = the 64 KiB counter block split-K uses, one
+   * arrival counter per (batch, row block); zero-filled before its first use, left zero after
+   * every launch; one in-flight launch per workspace. */
+  int norm;                /* 0 none, 1 LayerNorm, 2 RMSNorm */
+  const float* norm_w;
+  const float* norm_b;
+  float norm_eps;
+  float* norm_y32;
+  void* norm_y16;
+  float* norm_mean;
+  float* norm_rstd;
+  long long stride_norm_w, stride_norm_y, stride_norm_stat;
+  vqa_dropout norm_drop;
 } vqa_gemm_desc;
 
 /* tile configs: 1 128x128/3 stages, 2 128x64/4, 3 64x64/4, 4 64x64/2, 5 64x64/3, 6 128x64/2,
@@ -154,12 +184,14 @@ int vqa_quant_rows_fp8(const void* x, int x_bf16, long long ldx, int rows, int c
                        float* scale, hipStream_t stream);
 /* tile configuration (1..VQA_GEMM_CONFIGS) that vqa_gemm would run for this descriptor */
 int vqa_gemm_select(const vqa_gemm_desc* d);
-/* workspace bytes vqa_gemm needs for d (its config and splitk; 0 when splitk <= 1) */
+/* workspace bytes vqa_gemm needs for d (its config and splitk; 0 when splitk <= 1; the 64 KiB
+ * counter block for a norm descriptor) */
 long long vqa_gemm_workspace_bytes(const vqa_gemm_desc* d);
 /* Two independent GEMMs in one launch: a layer's input gradient dX (a_trans=0,
  * b_trans=1) and weight gradient dW (a_trans=1, b_trans=1), both batch 1, no
  * conv.  Each keeps its own epilogue and tile config (configs 3, 4, 6, 7; others
- * map to 4).  Any other pair of descriptors runs as two vqa_gemm calls. */
+ * map to 4).  Any other pair of descriptors runs as two vqa_gemm calls.  A descriptor with
+ * norm != 0 is rejected (VQA_ERR_INVALID): the paired kernel has no norm tail. */
 int vqa_gemm_pair(const vqa_gemm_desc* dx, const vqa_gemm_desc* dw, hipStream_t stream);
 
 /* ------------------------------------------------------------- attention ---

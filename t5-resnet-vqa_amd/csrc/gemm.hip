@@ -167,13 +167,25 @@ int patch_auto_config(const vqa_gemm_desc* d) {
 }
 }  // namespace
 
+namespace {
+// auto tile of a norm descriptor: only configs with a norm tail (e4m3: the 64x64 / 2 tile, as
+// vqa_gemm runs config 0 there)
+int norm_auto_config(const vqa_gemm_desc* d) {
+  if (d->fp8) return 4;
+  const int c = auto_config(d->m, d->n, d->k, d->batch);
+  return c == 3 || c == 4 ? c : 3;
+}
+}  // namespace
+
 extern "C" int vqa_gemm_select(const vqa_gemm_desc* d) {
   if (!d) return 0;
   if (d->config) return d->config;
+  if (d->norm) return norm_auto_config(d);
   return d->a_conv == 2 ? patch_auto_config(d) : auto_config(d->m, d->n, d->k, d->batch);
 }
 
 extern "C" long long vqa_gemm_workspace_bytes(const vqa_gemm_desc* d) {
+  if (d && d->norm) return NORM_CNT_BYTES;               // one arrival counter per (batch, row block)
   if (!d || d->splitk <= 1 || d->a_conv == 2) return 0;
   int bm, bn, kper;
   tile_of(vqa_gemm_select(d), bm, bn);
@@ -265,13 +277,65 @@ static int prepare(const vqa_gemm_desc* d, GemmParams& P) {
   return VQA_OK;
 }
 
+// vqa_gemm_desc.norm: validate (every rejection before anything is launched) and fill Q
+static int prepare_norm(const vqa_gemm_desc* d, const GemmParams& P, NormParams& Q) {
+  auto al = [](const void* p, int bytes) { return p == nullptr || ((uintptr_t)p % bytes) == 0; };
+  VQA_REQUIRE(d->norm == 1 || d->norm == 2, "vqa_gemm(norm): norm must be 0, 1 (LayerNorm) or 2 (RMSNorm)");
+  VQA_REQUIRE(d->c32 && d->ldc32 == d->n, "vqa_gemm(norm): needs c32 with ldc32 == n");
+  VQA_REQUIRE(d->n % 256 == 0 && d->n <= 1024, "vqa_gemm(norm): n=%d unsupported (n %% 256 == 0, <= 1024)", d->n);
+  VQA_REQUIRE(d->beta == 0.f && d->relu == 0, "vqa_gemm(norm): takes no beta and no activation");
+  VQA_REQUIRE(!d->a_trans && !d->b_trans && !d->a_conv && !d->b_conv,
+              "vqa_gemm(norm): k-contiguous A and B, no conv operand");
+  VQA_REQUIRE(d->splitk <= 1, "vqa_gemm(norm): takes no split-K");
+  VQA_REQUIRE(!d->mask16, "vqa_gemm(norm): takes no mask16");
+  VQA_REQUIRE(P.vec, "vqa_gemm(norm): needs the vectorised epilogue (ld*, strides multiples of 8, aligned pointers)");
+  VQA_REQUIRE(d->workspace && aligned16(d->workspace) && d->workspace_bytes >= NORM_CNT_BYTES,
+              "vqa_gemm(norm): needs a 16-byte aligned workspace of >= %lld bytes", NORM_CNT_BYTES);
+  const int cfg = d->config;
+  VQA_REQUIRE(cfg == 0 || (cfg >= 3 && cfg <= 7) || cfg == 21,
+              "vqa_gemm(norm): tile config %d has no norm tail (0, 3-7, 21)", cfg);
+  int bm, bn;                                             // one counter per (batch, row block of the tile's BM rows)
+  tile_of(cfg ? cfg : norm_auto_config(d), bm, bn);
+  VQA_REQUIRE((long long)vqa::cdiv(d->m, bm) * d->batch <= NORM_MAX_BLOCKS,
+              "vqa_gemm(norm): %lld (batch, row block) pairs at %d-row tiles, needs <= %lld",
+              (long long)vqa::cdiv(d->m, bm) * d->batch, bm, NORM_MAX_BLOCKS);
+  VQA_REQUIRE(d->norm_w && (d->norm_y32 || d->norm_y16), "vqa_gemm(norm): needs norm_w and norm_y32 or norm_y16");
+  VQA_REQUIRE(al(d->norm_w, 16) && al(d->norm_b, 16) && al(d->norm_y32, 16) && al(d->norm_y16, 8) &&
+                  al(d->norm_mean, 4) && al(d->norm_rstd, 4) && d->stride_norm_w % 4 == 0 && d->stride_norm_y % 4 == 0,
+              "vqa_gemm(norm): norm_w / norm_b / norm_y32 16-byte, norm_y16 8-byte aligned, strides multiples of 4");
+  const bool drop_on = d->norm_drop.p != 0.f && d->norm_drop.rng;
+  if (d->norm == 1) {
+    VQA_REQUIRE(d->norm_b && d->norm_mean && d->norm_rstd, "vqa_gemm(norm): LayerNorm needs norm_b, norm_mean, norm_rstd");
+    VQA_REQUIRE(!drop_on, "vqa_gemm(norm): norm_drop is for RMSNorm only");
+  } else {
+    VQA_REQUIRE(!d->norm_b && !d->norm_mean, "vqa_gemm(norm): RMSNorm takes no norm_b and no norm_mean");
+    VQA_REQUIRE(d->norm_drop.p >= 0.f && d->norm_drop.p < 1.f, "vqa_gemm(norm): dropout p must be in [0, 1)");
+    VQA_REQUIRE(!drop_on || d->batch == 1, "vqa_gemm(norm): norm_drop needs batch 1");
+  }
+  Q.kind = d->norm;
+  Q.eps = d->norm_eps;
+  Q.w = d->norm_w; Q.b = d->norm_b;
+  Q.y32 = d->norm_y32; Q.y16 = (bf16_t*)d->norm_y16; Q.mean = d->norm_mean; Q.rstd = d->norm_rstd;
+  Q.sw = d->stride_norm_w; Q.sy = d->stride_norm_y; Q.sstat = d->stride_norm_stat;
+  Q.drop = d->norm_drop;
+  Q.cnt = reinterpret_cast<unsigned*>(d->workspace);
+  return VQA_OK;
+}
+
 #ifndef VQA_GEMM_MICRO
 int vqa_gemm_fp8_dispatch(void* P, int batch, int config, hipStream_t s);   // gemm_fp8.hip
+int vqa_gemm_norm_dispatch(void* P, void* Q, int batch, int config, int fp8, hipStream_t s);   // gemm_norm.hip
 
 extern "C" int vqa_gemm(const vqa_gemm_desc* d, hipStream_t stream) {
   GemmParams P;
   if (int rc = prepare(d, P)) return rc;
   const int batch = d->batch, cfg = d->config;
+  if (d->norm) {                                          // GEMM + row norm (gemm_norm_kernel)
+    NormParams Q;
+    if (int rc = prepare_norm(d, P, Q)) return rc;
+    const int nc = cfg ? cfg : norm_auto_config(d);           // auto: only configs with a norm tail
+    return vqa_gemm_norm_dispatch(&P, &Q, batch, nc, d->fp8 != 0, stream);
+  }
   if (d->fp8) return vqa_gemm_fp8_dispatch(&P, batch, cfg, stream);
   const bool akc = !d->a_trans, bkc = !d->b_trans;
   const bool patch_cfg = (cfg >= VQA_GEMM_PATCH_FIRST && cfg <= VQA_GEMM_PATCH_LAST) || cfg == VQA_GEMM_PATCH_WIDE;
@@ -338,6 +402,7 @@ extern "C" int vqa_gemm_pair(const vqa_gemm_desc* dx, const vqa_gemm_desc* dw, h
   GemmParams P1, P2;
   if (int rc = prepare(dx, P1)) return rc;
   if (int rc = prepare(dw, P2)) return rc;
+  VQA_REQUIRE(!dx->norm && !dw->norm, "vqa_gemm_pair: takes no norm descriptor (use vqa_gemm)");
   const bool shape_ok = !dx->a_trans && dx->b_trans && !dx->a_conv && !dx->b_conv && dx->batch == 1 &&
                         dw->a_trans && dw->b_trans && !dw->a_conv && !dw->b_conv && dw->batch == 1 &&
                         P1.splitk == 1 && P2.splitk == 1;

@@ -1,19 +1,16 @@
-// The GEMM tile body, its kernel and launcher, shared by gemm.hip (bf16 operands) and
-// gemm_fp8.hip (e4m3 operands, BASELINE config 5's forward weight GEMMs), which compile as
-// separate translation units.
+// The GEMM tile body, its kernel and launcher, shared by gemm.hip (bf16 operands),
+// gemm_fp8.hip (e4m3 operands, BASELINE config 5's forward weight GEMMs) and gemm_norm.hip (the
+// NORM instantiations: a row norm behind the epilogue), which compile as separate translation
+// units.
 #pragma once
 #include "gemm_common.h"
-
-// diagnostic phase stamps (tools/micro/gemm_stamps.hip defines it; a no-op in the library)
-#ifndef VQA_GEMM_STAMP
-#define VQA_GEMM_STAMP(i)
-#endif
 
 namespace {
 
 template <int BM, int BN, int STAGES, int NWM, int NWN, bool AKC, bool BKC, bool GA, bool GB, bool EXT = false,
-          int BKT = BK, bool F8 = false>
-__device__ __forceinline__ void gemm_body(const GemmParams& P, const int bid, char* smem) {
+          int BKT = BK, bool F8 = false, bool NORM = false>
+__device__ __forceinline__ void gemm_body(const GemmParams& P, const int bid, char* smem,
+                                          const NormParams* Q = nullptr) {
   constexpr int NW = NWM * NWN, NT = 64 * NW;
   constexpr int WM = BM / NWM, WN = BN / NWN, TM = WM / 32, TN = WN / 32;
   static_assert(TM >= 1 && TN >= 1 && WM % 32 == 0 && WN % 32 == 0, "wave sub-tile must be whole 32x32 blocks");
@@ -245,6 +242,10 @@ __device__ __forceinline__ void gemm_body(const GemmParams& P, const int bid, ch
   VQA_GEMM_STAMP(3);
   tile_epilogue<BM, BN, STAGES, NWM, NWN, EXT, BKT>(P, acc, z, m0, n0, P.m, smem);
   VQA_GEMM_STAMP(4);
+  if constexpr (NORM) {                                // vqa_gemm_desc.norm: the row block's last tile normalises it
+    norm_tail<BM, NW>(P, *Q, z, tm, smem);
+    VQA_GEMM_STAMP(5);
+  }
 }
 
 template <int BM, int BN, int STAGES, int NWM, int NWN, bool AKC, bool BKC, bool GA, bool GB, int BKT = BK,
@@ -253,6 +254,11 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_kernel(GemmParams P) {
   __shared__ __attribute__((aligned(1024))) char smem[TileCfg<BM, BN, STAGES, BKT>::LDS];
   gemm_body<BM, BN, STAGES, NWM, NWN, AKC, BKC, GA, GB, false, BKT, F8>(P, blockIdx.x, smem);
 }
+
+// vqa_gemm_desc.norm: the workspace's leading counter block (as split-K's), one arrival
+// counter per (batch, row block); the kernels live in gemm_norm.hip
+constexpr long long NORM_CNT_BYTES = 65536;
+constexpr long long NORM_MAX_BLOCKS = NORM_CNT_BYTES / 4;
 
 // One k-tile (K <= 64: the frozen ResNet's 1x1 convolutions over 64 channels, tile configs 26-28):
 // the ring's second stage is never filled (the prologue issues k-tile 0 into stage 0 and the loop

@@ -1,10 +1,17 @@
 // Device-side building blocks shared by the GEMM / implicit-GEMM convolution kernels
 // (gemm.hip) and the LDS-patch 3x3 convolution (conv_patch.hip): the parameter block,
-// the LDS-DMA operand loaders, the fragment readers, the counted waits and the fused
-// epilogue.  Included by exactly those translation units (anonymous namespace: each
+// the LDS-DMA operand loaders, the fragment readers, the counted waits, the fused
+// epilogue and the row-norm tail behind it.  Included by exactly those translation units (anonymous namespace: each
 // code object gets its own copy).
 #pragma once
 #include "common.h"
+#include "norm_rows.h"
+
+// diagnostic phase stamps (tools/micro/gemm_stamps.hip and gemm_norm_micro.hip define it; a
+// no-op in the library)
+#ifndef VQA_GEMM_STAMP
+#define VQA_GEMM_STAMP(i)
+#endif
 
 static __device__ __attribute__((aligned(64))) uint4 vqa_zero_page[4];   // zero-initialised code-object global
 
@@ -37,6 +44,19 @@ struct GemmParams {
   // 2 bytes, so the bf16 loaders stage them unchanged); acc(m, n) is scaled by qsa[m] * qsb[n]
   const float* qsa; const float* qsb;
   long sqa, sqb;           // scale strides per batch element
+};
+
+// Row norm fused behind the tile epilogue (vqa_gemm_desc.norm; norm_tail below).  A block of
+// its own, passed beside GemmParams to the norm kernels only, so the kernel arguments of
+// every other kernel of the family keep their layout.
+struct NormParams {
+  int kind;                // 1 LayerNorm, 2 RMSNorm
+  float eps;
+  const float* w; const float* b;
+  float* y32; bf16_t* y16; float* mean; float* rstd;
+  long sw, sy, sstat;      // batch strides: w / b, y32 / y16, mean / rstd (signed)
+  vqa_dropout drop;        // dropout of y, element row*n + col (RMSNorm)
+  unsigned* cnt;           // [batch][tiles_m] arrival counters (zero between launches)
 };
 
 // byte offset of 16-B chunk `ch` of row `row` in a k-contig image ([rows][BKT bf16]):
@@ -547,6 +567,88 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& P, f32x16_t (&ac
           }
           if (C16) C16[(long)row * P.ldc16 + col] = f2bf(v);
         }
+  }
+}
+
+// ---------------------------------------------------------------- row-norm tail
+// Runs behind tile_epilogue in the NORM instantiations (vqa_gemm_desc.norm): the workgroup
+// publishes the fp32 c32 tile it has just stored and counts itself on the counter of its
+// (batch z, row block tm); the workgroup that arrives last of the row block's tiles_n column
+// tiles resets the counter, reads the whole BM x n row block of c32 back and writes the
+// normalised rows -- one wave per row, rows w, w + NW, ..., the arithmetic of norm_rows.h.
+// Nobody waits for anybody (nothing can hang) and the rows do not depend on arrival order.
+//
+// Hand-off (cdna_hip_programming.md, split-K item 2 / Guideline 16, the plain-store form):
+// the epilogue's c32 stores stay plain; every storing wave drains them (vmcnt(0)), the
+// barrier, then lane 0: agent-scope release fence, vmcnt(0), relaxed agent-scope fetch_add.
+// The last arriver: lane 0 agent-scope acquire fence, vmcnt(0), the barrier, then plain
+// loads by every wave.  "I am last" travels through the first word of the LDS ring (idle
+// after the epilogue's last sweep, which the first barrier here closes).
+template <int NV>
+__device__ __forceinline__ void norm_rows_block(const NormParams& Q, const float* __restrict__ x, const int z,
+                                                const int row0, const int nrows, const int w, const int nw) {
+  constexpr int D = NV * 256;
+  const float* W = Q.w + (long)z * Q.sw;
+  const float* Bv = Q.b ? Q.b + (long)z * Q.sw : nullptr;
+  float* Y32 = Q.y32 ? Q.y32 + (long)z * Q.sy : nullptr;
+  bf16_t* Y16 = Q.y16 ? Q.y16 + (long)z * Q.sy : nullptr;
+  float* MU = Q.mean ? Q.mean + (long)z * Q.sstat : nullptr;
+  float* RS = Q.rstd ? Q.rstd + (long)z * Q.sstat : nullptr;
+  const DropK dk = drop_init(Q.drop);
+  float g[NV][4], b[NV][4];
+  load_vec<NV>(W, g);
+  if (Q.kind == 1) load_vec<NV>(Bv, b);
+  for (int r = w; r < nrows; r += nw) {                 // rows at or beyond m: neither read nor written
+    const int row = row0 + r;
+    float v[NV][4];
+    load_row<NV>(x + (long)row * D, v);
+    float mu = 0.f, rs;
+    if (Q.kind == 1) {
+      rs = layernorm_stats<NV>(v, Q.eps, mu);
+      layernorm_apply<NV>(v, mu, rs, g, b);
+    } else {
+      rs = rmsnorm_row<NV>(v, g, Q.eps);
+      drop_row<NV>(dk, row, v);
+    }
+    if (Y32) store_row32<NV>(Y32 + (long)row * D, v);
+    if (Y16) store_row16<NV>(Y16 + (long)row * D, v);
+    if ((threadIdx.x & 63) == 0) {
+      if (MU) MU[row] = mu;
+      if (RS) RS[row] = rs;
+    }
+  }
+}
+
+template <int BM, int NW>
+__device__ __forceinline__ void norm_tail(const GemmParams& P, const NormParams& Q, const int z, const int tm,
+                                          char* smem) {
+  typedef __attribute__((address_space(1))) unsigned gu32;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // EVERY storing wave drains its c32 stores
+  __syncthreads();                                      // ... and is done with the epilogue's LDS image
+  int* flag = reinterpret_cast<int*>(smem);
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // keep: the fence's own wait can be dropped
+    gu32* c = (gu32*)(Q.cnt + (long)z * P.tiles_m + tm);
+    const unsigned prev = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = prev == (unsigned)(P.tiles_n - 1);
+    if (last) {
+      __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // zero for the next launch
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // holds the barrier for the invalidate
+    }
+    *flag = last;
+  }
+  __syncthreads();
+  if (!*flag) return;
+  VQA_GEMM_STAMP(6);                                    // (the last arriver only)
+  const float* x = P.c32 + (long)z * P.sc32;            // ldc32 == n (host check): rows are contiguous
+  const int row0 = tm * BM, nrows = min(BM, P.m - row0), w = threadIdx.x >> 6;
+  switch (P.n >> 8) {                                   // n % 256 == 0, n <= 1024 (host check)
+    case 1: norm_rows_block<1>(Q, x, z, row0, nrows, w, NW); break;
+    case 2: norm_rows_block<2>(Q, x, z, row0, nrows, w, NW); break;
+    case 3: norm_rows_block<3>(Q, x, z, row0, nrows, w, NW); break;
+    default: norm_rows_block<4>(Q, x, z, row0, nrows, w, NW); break;
   }
 }
 

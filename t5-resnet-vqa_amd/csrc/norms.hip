@@ -6,53 +6,13 @@
 // a workspace [gridDim.x][D] that vqa_colsum_partials() reduces
 // deterministically (no atomics).
 #include "common.h"
+#include "norm_rows.h"
 
 namespace {
 
 constexpr int ROWS_PER_BLOCK = 4;       // 4 waves, one row each
 constexpr int MAXV = 4;                 // up to 4 float4 per lane -> D <= 1024
 
-template <int NV>
-__device__ __forceinline__ void load_row(const float* __restrict__ p, float (&x)[NV][4]) {
-  const int l = threadIdx.x & 63;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    float4 v = reinterpret_cast<const float4*>(p)[i * 64 + l];
-    x[i][0] = v.x; x[i][1] = v.y; x[i][2] = v.z; x[i][3] = v.w;
-  }
-}
-template <int NV>
-__device__ __forceinline__ void store_row32(float* __restrict__ p, const float (&x)[NV][4]) {
-  const int l = threadIdx.x & 63;
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-    reinterpret_cast<float4*>(p)[i * 64 + l] = make_float4(x[i][0], x[i][1], x[i][2], x[i][3]);
-}
-template <int NV>
-__device__ __forceinline__ void store_row16(bf16_t* __restrict__ p, const float (&x)[NV][4]) {
-  const int l = threadIdx.x & 63;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    uint2 u;
-    u.x = (uint32_t)f2bf(x[i][0]) | ((uint32_t)f2bf(x[i][1]) << 16);
-    u.y = (uint32_t)f2bf(x[i][2]) | ((uint32_t)f2bf(x[i][3]) << 16);
-    reinterpret_cast<uint2*>(p)[i * 64 + l] = u;
-  }
-}
-template <int NV>
-__device__ __forceinline__ void load_vec(const float* __restrict__ p, float (&x)[NV][4]) { load_row<NV>(p, x); }
-
-// multiply a row held as [NV][4] per lane by the dropout factors of row `row`
-template <int NV>
-__device__ __forceinline__ void drop_row(const DropK& k, int row, float (&x)[NV][4]) {
-  if (!k.on) return;
-  const int l = threadIdx.x & 63;
-  const uint32_t base = (uint32_t)row * (uint32_t)(NV * 256);
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[i][j] *= drop_mul(k, base + (uint32_t)((i * 64 + l) * 4 + j));
-}
 template <int NV>
 __device__ __forceinline__ void store_row16_drop(bf16_t* __restrict__ p, const DropK& k, int row,
                                                  const float (&x)[NV][4]) {
@@ -91,17 +51,7 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const float* __restric
   float v[NV][4], g[NV][4];
   load_row<NV>(x + (long)row * D, v);
   load_vec<NV>(w, g);
-  float ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ss += v[i][j] * v[i][j];
-  ss = wave_sum(ss);
-  const float r = rsqrtf(ss / D + eps);
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[i][j] = g[i][j] * (v[i][j] * r);
+  const float r = rmsnorm_row<NV>(v, g, eps);
   drop_row<NV>(dk, row, v);
   if (y32) store_row32<NV>(y32 + (long)row * D, v);
   if (y16) store_row16<NV>(y16 + (long)row * D, v);
@@ -189,24 +139,11 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
   constexpr int D = NV * 256;
   float v[NV][4], g[NV][4], b[NV][4];
   load_row<NV>(x + (long)row * D, v);
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s += v[i][j];
-  const float mu = wave_sum(s) / D;
-  float ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { float t = v[i][j] - mu; ss += t * t; }
-  const float r = rsqrtf(wave_sum(ss) / D + eps);
+  float mu;
+  const float r = layernorm_stats<NV>(v, eps, mu);
   load_vec<NV>(gam, g);
   load_vec<NV>(bet, b);
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[i][j] = (v[i][j] - mu) * r * g[i][j] + b[i][j];
+  layernorm_apply<NV>(v, mu, r, g, b);
   if (y32) store_row32<NV>(y32 + (long)row * D, v);
   if (y16) store_row16<NV>(y16 + (long)row * D, v);
   if ((threadIdx.x & 63) == 0) { mean_out[row] = mu; rstd_out[row] = r; }

@@ -84,7 +84,7 @@ def _gemm_key(d):
     return (d.m, d.n, d.k, d.batch, d.a_trans, d.b_trans, d.a_conv, d.b_conv,
             geo(d.ga) if d.a_conv else None, geo(d.gb) if d.b_conv else None,
             bool(d.c32), bool(d.c16), bool(d.bias), bool(d.res32), bool(d.res16), bool(d.mask16), d.relu,
-            d.beta != 0.0, d.drop.p > 0.0) + (("fp8",) if d.fp8 else ())
+            d.beta != 0.0, d.drop.p > 0.0) + (("fp8",) if d.fp8 else ()) + (("norm", d.norm) if d.norm else ())
 
 
 class _Seq:
@@ -185,8 +185,13 @@ class VQAEngine:
                  warmup=10, total=100, num_blocks=3, answer_spaces=170, grad_scale=1.0, max_norm=1.0,
                  betas=(0.9, 0.999), eps=1e-8, weight_decay=0.1, dropout=0.1, seed=0, pipeline=False,
                  t5_dw_group=None, defer_optimizer=True, dw_stream=None, sga_dw_batch=True, pair_bwd=True,
-                 language_model="t5-base", fp8=False, sga_attn_group=True):
+                 language_model="t5-base", fp8=False, sga_attn_group=True, fuse_norm=None):
         L.load()
+        # fuse_norm: every forward LayerNorm / RMSNorm but layer 0's ln0 runs as the tail of the
+        # GEMM that writes its input (vqa_gemm_desc.norm) instead of as a launch of its own;
+        # same bits.  Opt-in; None reads the environment (VQA_FUSE_NORM=1), like VQA_STEM.
+        self.fuse_norm = (os.environ.get("VQA_FUSE_NORM", "0") == "1") if fuse_norm is None else bool(fuse_norm)
+        self.fuse_norm_kept = []          # norms left stand-alone although fuse_norm is on, with the reason
         # pipeline: the frozen ResNet (no trainable input) of the NEXT batch runs on its own
         # stream beside this step's T5 / SGA / backward / optimizer (see train_step)
         self.pipeline = bool(pipeline)
@@ -504,6 +509,16 @@ class VQAEngine:
         # (slot NB-1-n) for the batched dW launches
         self.X1hS, self.O2S, self.X2hS, self.FFhS = (t((NB, T, D), BF16) for _ in range(4))
         self.Q2S = t((NB, T, D), BF16)                 # the blocks' cross-attention queries (one batched GEMM)
+        if self.fuse_norm:
+            # the batched merge writes every block's norm1 outputs: one signed stride per output
+            # kind, so X1 is stacked like X1hS (slot NB-1-n), the statistics in block order
+            self.X1S, self.MU1S, self.RS1S = t((NB, T, D)), t((NB, T)), t((NB, T))
+            # arrival counters of the norm-carrying GEMMs (zero-filled, left zero by every launch):
+            # one block for the T5 encoder's chain and one for the SGA blocks'.  Each chain is
+            # serial on its stream; the two never overlap (the fusion segment starts after the
+            # text branch has joined), and neither the vision branch beside the encoder nor the
+            # pipelined ResNet of the next batch has a norm-carrying GEMM
+            self.NORM_WS = [torch.zeros(65536 // 4, dtype=torch.int32, device=self.dev) for _ in range(2)]
         self.sga = []
         for n in range(NB):
             ly = V if n == 0 else T
@@ -511,7 +526,8 @@ class VQAEngine:
             self.sga.append(dict(
                 ly=ly, lk=lk,
                 P1=self.P1A[n], O1=self.O1A[n], S1=self.S1A[n],
-                X1=t((T, D)), X1h=self.X1hS[NB - 1 - n], MU1=t(T), RS1=t(T),
+                X1=self.X1S[NB - 1 - n] if self.fuse_norm else t((T, D)), X1h=self.X1hS[NB - 1 - n],
+                MU1=self.MU1S[n] if self.fuse_norm else t(T), RS1=self.RS1S[n] if self.fuse_norm else t(T),
                 Q2=self.Q2S[NB - 1 - n], KV2=t((ly, 2 * D), BF16), P2=t((B, self.sga_heads, Lq, lk)),
                 O2=self.O2S[NB - 1 - n], S2=t((T, D)), X2=t((T, D)), X2h=self.X2hS[NB - 1 - n], MU2=t(T), RS2=t(T),
                 FFh=self.FFhS[NB - 1 - n], S3=t((T, D)), OUT=t((T, D)), OUTh=t((T, D), BF16), MU3=t(T), RS3=t(T)))
@@ -645,14 +661,19 @@ class VQAEngine:
         self._call(lst, "vqa_quant_rows_fp8", x16, 1, k, rows, k, x8, k, xs)
         return x8, xs
 
-    def _linear(self, lst, x16, wname, m, out32=None, out16=None, bias=True, relu=False, res32=None, drop=None):
+    def _linear(self, lst, x16, wname, m, out32=None, out16=None, bias=True, relu=False, res32=None, drop=None,
+                norm=None):
+        """norm: vqa_gemm_desc norm fields (ops.gemm_desc keywords) of a row norm fused behind
+        this GEMM (fuse_norm), or None."""
+        nkw = dict(norm or {})
+        nkeep = tuple(nkw.pop("keep", ()))
         if getattr(self, "fp8", False) and self._is_fp8(wname):          # (borrowed by VitVQAEngine: no fp8)
             x8, xs = self._quant_act(lst, (wname, "x"), x16, m)
             w8, ws = self._w8(wname)
             n, k = w8.shape
             self._gemm(lst, x8, w8, m, n, k, lda=k, ldb=k, c32=out32, ldc32=n, c16=out16, ldc16=n,
                        bias=self.p32[wname[:-1] + "b"] if bias else None, relu=relu, res32=res32, ldres=n, fp8=True,
-                       scale_a=xs, scale_b=ws, keep=(self.W8, self.WSC))
+                       scale_a=xs, scale_b=ws, keep=(self.W8, self.WSC) + nkeep, **nkw)
             d = self._drop(drop) if drop is not None else None
             if d is not None:
                 lst[-1].desc.drop = d
@@ -661,11 +682,24 @@ class VQAEngine:
         w = self.p16[wname]
         n, k = w.shape
         self._gemm(lst, x16, w, m, n, k, lda=k, ldb=k, c32=out32, ldc32=n, c16=out16, ldc16=n,
-                   bias=self.p32[wname[:-1] + "b"] if bias else None, relu=relu, res32=res32, ldres=n)
+                   bias=self.p32[wname[:-1] + "b"] if bias else None, relu=relu, res32=res32, ldres=n, keep=nkeep, **nkw)
         d = self._drop(drop) if drop is not None else None
         if d is not None:
             lst[-1].desc.drop = d
             lst[-1].keep = lst[-1].keep + (self.RNG,)
+
+    def _rms_kw(self, w, y16, rstd, ws, y32=None, drop=None):
+        """ops.gemm_desc keywords of a T5 RMSNorm fused behind the GEMM that writes its input."""
+        kw = dict(norm=L.NORM_RMS, norm_w=w, norm_eps=1e-6, norm_y32=y32, norm_y16=y16, norm_rstd=rstd, workspace=ws)
+        d = self._drop(drop) if drop is not None else None
+        if d is not None:
+            kw.update(norm_drop=d, keep=(self.RNG,))
+        return kw
+
+    def _ln_kw(self, g, b, y32, y16, mean, rstd, ws, **strides):
+        """... of an SGA LayerNorm."""
+        return dict(norm=L.NORM_LAYER, norm_w=g, norm_b=b, norm_eps=1e-5, norm_y32=y32, norm_y16=y16, norm_mean=mean,
+                    norm_rstd=rstd, workspace=ws, **strides)
 
     def _dx(self, lst, dy16, wname, m, out32=None, out16=None, res32=None, mask16=None, beta=0.0, alpha=1.0):
         """dX[m, k] = alpha * dY[m, n] W[n, k]  (+res) (*mask>0) (+beta*out32)"""
@@ -746,6 +780,8 @@ class VQAEngine:
         D = self.D
         f = self.fwd_calls
         B, Lq, T = self.B, self.L, self.T
+        fuse = self.fuse_norm
+        wt5, wsga = self.NORM_WS if fuse else (None, None)   # arrival counters: T5 chain, SGA chain
         if self.p_drop > 0.0:                                # fresh dropout masks every step
             self._call(f, "vqa_rng_advance", self.RNG)
         self._fsplit = [len(f)]                              # [pre | vision | text | fusion]
@@ -770,8 +806,9 @@ class VQAEngine:
         self._t5_layer_start = []
         for i in range(self.nl):
             self._t5_layer_start.append(len(f))
-            self._call(f, "vqa_rmsnorm_fwd", self.HS[i], self.p32[f"t5.{i}.ln0"], None, self.N0[i], self.R0[i], T,
-                       D, 1e-6, None)
+            if i == 0 or not fuse:                           # fused: the previous layer's wo wrote N0 / R0
+                self._call(f, "vqa_rmsnorm_fwd", self.HS[i], self.p32[f"t5.{i}.ln0"], None, self.N0[i], self.R0[i],
+                           T, D, 1e-6, None)
             self._linear(f, self.N0[i], f"t5.{i}.qkv_w", T, out16=self.QKV[i], bias=False)
             q = self.QKV[i]
             self._attn(f, "vqa_attn_fwd", q=q, ldq=3 * D, k=ops.addr(q, D), ldk=3 * D, v=ops.addr(q, 2 * D),
@@ -779,17 +816,25 @@ class VQAEngine:
                        heads=self.h5, lq=Lq, lk=Lq, dh=self.dkv, scale=1.0, drop=t5_site(i, 0))
             # h + dropout(attention output)   (T5LayerSelfAttention :400)
             self._linear(f, self.O[i], f"t5.{i}.o_w", T, out32=self.HM[i], bias=False, res32=self.HS[i],
-                         drop=t5_site(i, 1))
+                         drop=t5_site(i, 1),
+                         norm=self._rms_kw(self.p32[f"t5.{i}.ln1"], self.N1[i], self.R1[i], wt5) if fuse else None)
             # dropout(relu(wi h)) (T5DenseActDense :86), then h + dropout(wo .) (T5LayerFF :140)
-            self._call(f, "vqa_rmsnorm_fwd", self.HM[i], self.p32[f"t5.{i}.ln1"], None, self.N1[i], self.R1[i], T,
-                       D, 1e-6, None)
+            if not fuse:
+                self._call(f, "vqa_rmsnorm_fwd", self.HM[i], self.p32[f"t5.{i}.ln1"], None, self.N1[i], self.R1[i],
+                           T, D, 1e-6, None)
             self._linear(f, self.N1[i], f"t5.{i}.wi", T, out16=self.FF[i], bias=False, relu=True,
                          drop=t5_site(i, 2))
+            nrm = None
+            if fuse and i + 1 < self.nl:                     # wo carries the next layer's ln0 ...
+                nrm = self._rms_kw(self.p32[f"t5.{i + 1}.ln0"], self.N0[i + 1], self.R0[i + 1], wt5)
+            elif fuse:                                       # ... the last one the final norm and its dropout
+                nrm = self._rms_kw(self.p32["t5.final_ln"], self.TXT16, self.RF, wt5, y32=self.TXT32, drop=SITE_FINAL)
             self._linear(f, self.FF[i], f"t5.{i}.wo", T, out32=self.HS[i + 1], bias=False, res32=self.HM[i],
-                         drop=t5_site(i, 3))
-        kp = []
-        self._call(f, "vqa_rmsnorm_fwd", self.HS[-1], self.p32["t5.final_ln"], self.TXT32, self.TXT16, self.RF, T, D,
-                   1e-6, self._dptr(SITE_FINAL, kp), extra=kp + [self.RNG])
+                         drop=t5_site(i, 3), norm=nrm)
+        if not fuse:
+            kp = []
+            self._call(f, "vqa_rmsnorm_fwd", self.HS[-1], self.p32["t5.final_ln"], self.TXT32, self.TXT16, self.RF, T,
+                       D, 1e-6, self._dptr(SITE_FINAL, kp), extra=kp + [self.RNG])
         self._fsplit.append(len(f))
         # SGA blocks: x = text always, y chained
         y16 = self.VIS16
@@ -818,16 +863,35 @@ class VQAEngine:
         m1kw = dict(c32=self.S1A, ldc32=D, bias=self.p32["sga0.m1_b"], res32=self.TXT32, ldres=D, batch=NB,
                     stride_a=T * D, stride_b=D * D, stride_c32=T * D, stride_res=0, stride_bias=D,
                     drop_site_stride=sga_site(1, 1) - sga_site(0, 1))
+        fuse1 = fuse
+        if fuse and NB > 1:
+            # the merge is one launch over the blocks: their gamma / beta must sit at one stride
+            gs = [self.lay[f"sga{n}.ln1_g"].offset for n in range(NB)]
+            bs = [self.lay[f"sga{n}.ln1_b"].offset for n in range(NB)]
+            gst = gs[1] - gs[0]
+            fuse1 = all(b_ - a_ == gst for a_, b_ in zip(gs, gs[1:])) and \
+                all(b_ - a_ == gst for a_, b_ in zip(bs, bs[1:])) and gst % 4 == 0
+            if not fuse1:
+                self.fuse_norm_kept.append("sga ln1: gamma / beta of the blocks are not at one constant stride")
+        if fuse1:
+            gst = (self.lay["sga1.ln1_g"].offset - self.lay["sga0.ln1_g"].offset) if NB > 1 else 0
+            m1kw.update(self._ln_kw(self.p32["sga0.ln1_g"], self.p32["sga0.ln1_b"], self.X1S[NB - 1], self.X1hS[NB - 1],
+                                    self.MU1S, self.RS1S, wsga, stride_norm_w=gst, stride_norm_y=-T * D,
+                                    stride_norm_stat=T))
+            m1keep = (self.P32, self.X1S, self.X1hS)
+        else:
+            m1keep = ()
         if self.fp8:
             x8, xs = self._quant_act(f, ("sga.m1", "x"), self.O1A.view(NB * T, D), NB * T)
             o0 = self.lay["sga0.m1_w"].offset
             self._gemm(f, x8, self.W8[o0:], T, D, D, lda=D, ldb=D, fp8=True, scale_a=xs, stride_scale_a=T,
                        scale_b=ops.addr(self.WSC, o0), stride_scale_b=D * D,
-                       keep=self._sga_self_keep() + (self.W8, self.WSC), **m1kw)
+                       keep=self._sga_self_keep() + (self.W8, self.WSC) + m1keep, **m1kw)
         else:
-            self._gemm(f, self.O1A, self.p16["sga0.m1_w"], T, D, D, lda=D, ldb=D, keep=self._sga_self_keep(), **m1kw)
+            self._gemm(f, self.O1A, self.p16["sga0.m1_w"], T, D, D, lda=D, ldb=D,
+                       keep=self._sga_self_keep() + m1keep, **m1kw)
         self._set_drop(f[-1], sga_site(0, 1))
-        for n in range(NB):
+        for n in range(NB if not fuse1 else 0):
             s, p = self.sga[n], f"sga{n}."
             self._call(f, "vqa_layernorm_fwd", s["S1"], self.p32[p + "ln1_g"], self.p32[p + "ln1_b"], s["X1"],
                        s["X1h"], s["MU1"], s["RS1"], T, D, 1e-5)
@@ -857,13 +921,19 @@ class VQAEngine:
             self._attn(f, "vqa_attn_fwd", q=s["Q2"], ldq=D, k=kv, ldk=2 * D, v=ops.addr(kv, D), ldv=2 * D,
                        o=s["O2"], ldo=D, p=s["P2"], batch=B, heads=self.sga_heads, lq=Lq, lk=s["lk"], dh=self.sga_dh,
                        scale=sc, drop=sga_site(n, 2))
-            self._linear(f, s["O2"], p + "m2_w", T, out32=s["S2"], res32=s["X1"], drop=sga_site(n, 3))
-            self._call(f, "vqa_layernorm_fwd", s["S2"], self.p32[p + "ln2_g"], self.p32[p + "ln2_b"], s["X2"],
-                       s["X2h"], s["MU2"], s["RS2"], T, D, 1e-5)
+            self._linear(f, s["O2"], p + "m2_w", T, out32=s["S2"], res32=s["X1"], drop=sga_site(n, 3),
+                         norm=self._ln_kw(self.p32[p + "ln2_g"], self.p32[p + "ln2_b"], s["X2"], s["X2h"], s["MU2"],
+                                          s["RS2"], wsga) if fuse else None)
+            if not fuse:
+                self._call(f, "vqa_layernorm_fwd", s["S2"], self.p32[p + "ln2_g"], self.p32[p + "ln2_b"], s["X2"],
+                           s["X2h"], s["MU2"], s["RS2"], T, D, 1e-5)
             self._linear(f, s["X2h"], p + "fc1_w", T, out16=s["FFh"], relu=True, drop=sga_site(n, 4))
-            self._linear(f, s["FFh"], p + "fc2_w", T, out32=s["S3"], res32=s["X2"], drop=sga_site(n, 5))
-            self._call(f, "vqa_layernorm_fwd", s["S3"], self.p32[p + "ln3_g"], self.p32[p + "ln3_b"], s["OUT"],
-                       s["OUTh"], s["MU3"], s["RS3"], T, D, 1e-5)
+            self._linear(f, s["FFh"], p + "fc2_w", T, out32=s["S3"], res32=s["X2"], drop=sga_site(n, 5),
+                         norm=self._ln_kw(self.p32[p + "ln3_g"], self.p32[p + "ln3_b"], s["OUT"], s["OUTh"], s["MU3"],
+                                          s["RS3"], wsga) if fuse else None)
+            if not fuse:
+                self._call(f, "vqa_layernorm_fwd", s["S3"], self.p32[p + "ln3_g"], self.p32[p + "ln3_b"], s["OUT"],
+                           s["OUTh"], s["MU3"], s["RS3"], T, D, 1e-5)
             y16 = s["OUTh"]
         last = self.sga[-1]["OUT"]
         self._call(f, "vqa_head_fwd", last, self.p32["pool_w"], self.p32["pool_b"], self.p32["cls_w"],
@@ -1160,6 +1230,8 @@ class VQAEngine:
         # head).  The embedding table + rel-bias range is read by the forward's very first
         # calls, so it is applied at the end of step k instead (the T5 chain would otherwise
         # start behind its 0.9 GB pass).  Same arithmetic, same order of updates vs uses.
+        # (With fuse_norm a T5 layer's wo GEMM reads the next layer's ln0 gain, so the layer
+        # also waits for the next layer's range: _t5_waits.)
         lay = self.lay
         cuts = [("embed", lay["t5.relbias"].offset, n)]
         for i in range(self.nl):
@@ -1169,6 +1241,7 @@ class VQAEngine:
         cuts.append(("scaler", lay["scaler_w"].offset, lay["t5.final_ln"].offset))
         cuts.append(("head", 0, lay["scaler_w"].offset))     # classifier, pooler, SGA
         assert sum(hi - lo for _, lo, hi in cuts) == n
+        self.adam_cuts = {name: (lo, hi) for name, lo, hi in cuts}     # flat-arena range of each update
         # fp8: the e4m3 copies of the range's weights follow every AdamW range (and the whole
         # update when it is not deferred)
         quant = {name: [] for name, _, _ in cuts}
@@ -1420,11 +1493,22 @@ class VQAEngine:
             main.wait_event(join)
         self._run(f[p2:])                                  # SGA + head
 
+    def _t5_waits(self, i):
+        """The deferred AdamW ranges T5 layer i's calls must find applied, beyond those of the
+        layers before it: its own, and with fuse_norm also layer i+1's -- the layer's `wo` GEMM
+        then carries the NEXT layer's ln0 and reads that gain, which lies in range t5.{i+1}
+        (layout.py: a layer's range runs from its q|k|v weight to its ln1)."""
+        w = [f"t5.{i}"]
+        if self.fuse_norm and i + 1 < self.nl:
+            w.append(f"t5.{i + 1}")
+        return w
+
     def _forward_branches_deferred(self, fork, main, side, vis, txt):
         """The two forward branches with the previous step's AdamW ranges on a third stream.
         Capture order is submission order for a replayed graph, so the ranges are issued
         two T5 layers ahead of the layer calls that wait for them (issuing all of them
-        first held the T5 chain back ~0.47 ms); the vision branch's parameter-reading
+        first held the T5 chain back ~0.47 ms; with fuse_norm a layer also waits for the next
+        layer's range, _t5_waits); the vision branch's parameter-reading
         calls wait for the scaler range, the SGA / head for the last range."""
         hm, hs = L.stream_handle(main), L.stream_handle(side)
         # the ranges run on the vision-branch stream: a fourth concurrent stream shares a
@@ -1466,7 +1550,8 @@ class VQAEngine:
         for i in range(nl):
             if i + ahead < nl:
                 issue(f"t5.{i + ahead}")
-            side.wait_event(ev[f"t5.{i}"])
+            for name in self._t5_waits(i):                 # (fuse_norm: one layer of slack, not two)
+                side.wait_event(ev[name])
             for t in range(bounds[i], bounds[i + 1]):
                 txt[t](hs)
             res_upto(head + (i + 1) * (nres - head) // nl)
@@ -1741,6 +1826,9 @@ class VQAEngine:
         call gets its own zero-filled workspace, kept alive by the call."""
         d = c.desc
         d.config, sk = choice % 100, choice // 100
+        if d.norm:                                         # a norm tail: no split-K, its workspace stays
+            assert sk <= 1 and d.config in L.GEMM_NORM, choice
+            return
         if sk > 1:
             ops.set_splitk(d, sk)
             ws = ops.splitk_workspace(d, self.dev)
@@ -1825,12 +1913,20 @@ class VQAEngine:
                         continue
                     if d.fp8 and cfg not in L.GEMM_FP8:
                         continue
+                    if d.norm and cfg not in L.GEMM_NORM:
+                        continue                           # tile configs with a row-norm tail
                     bm, bn, _ = L.GEMM_TILES[cfg]
                     tiles = -(-d.m // bm) * -(-d.n // bn) * max(1, d.batch)
                     if cfg in L.GEMM_BK128 and (d.a_conv or d.b_conv):
                         continue                           # 128-deep k-tiles: plain operands only
                     if cfg in L.GEMM_K64_ONLY and (d.k > 64 or d.a_conv or d.b_conv):
                         continue                           # one k-tile, plain operands only
+                    if d.norm:                             # no split-K; the descriptor's workspace = its counters
+                        d.config = cfg
+                        t = time_call(c)
+                        if best is None or t < best[0]:
+                            best = (t, cfg)
+                        continue
                     for sk in SPLITS:
                         # split only grids that leave CUs idle, with >= 2 k-tiles per slice
                         if sk > 1 and (tiles >= 512 or nk < 2 * sk or tiles > 16384 or d.a_conv == 2
@@ -1842,7 +1938,8 @@ class VQAEngine:
                         t = time_call(c)
                         if best is None or t < best[0]:
                             best = (t, cfg + 100 * sk)
-                ops.set_splitk(d, 0)
+                if not d.norm:
+                    ops.set_splitk(d, 0)
                 cache[key] = best[1]
             self._apply_choice(c, cache[key])
             chosen[key] = cache[key]

@@ -50,6 +50,10 @@ class GemmDesc(ctypes.Structure):
         ("stride_bias", c_ll), ("drop_site_stride", c_int),
         ("fp8", c_int), ("scale_a", c_void_p), ("scale_b", c_void_p),
         ("stride_scale_a", c_ll), ("stride_scale_b", c_ll),
+        ("norm", c_int), ("norm_w", c_void_p), ("norm_b", c_void_p), ("norm_eps", c_float),
+        ("norm_y32", c_void_p), ("norm_y16", c_void_p), ("norm_mean", c_void_p), ("norm_rstd", c_void_p),
+        ("stride_norm_w", c_ll), ("stride_norm_y", c_ll), ("stride_norm_stat", c_ll),
+        ("norm_drop", Dropout),
     ]
 
 
@@ -90,6 +94,9 @@ GEMM_BK128 = (21, 22, 23, 24)            # 128-deep k-tiles: no implicit im2col 
 GEMM_K64_ONLY = (26, 27, 28)             # one k-tile in a single-stage ring: k <= 64, no implicit im2col, no split-K
 GEMM_FP8 = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 21, 22, 23)   # tile configs with an e4m3 form (gemm_fp8.hip)
 GEMM_WAVES = {c: ((4, 2) if c in (9, 12, 25) else (2, 4) if c in (10, 11, 24) else (2, 2)) for c in GEMM_TILES}
+
+GEMM_NORM = (3, 4, 5, 6, 7, 21)           # tile configs with a row-norm tail (vqa_gemm_desc.norm), bf16 and e4m3
+NORM_LAYER, NORM_RMS = 1, 2              # vqa_gemm_desc.norm
 
 ATTN_MFMA, ATTN_LONG, ATTN_VALU = 0, 1, 2          # vqa_attn_path
 MAX_GROUPS = 8

@@ -30,9 +30,14 @@ def gemm_desc(a, b, m, n, k, *, lda, ldb, a_trans=False, b_trans=False, c32=None
               bias=None, res32=None, res16=None, ldres=0, mask16=None, ldmask=0, alpha=1.0, beta=0.0,
               relu=False, ga=None, gb=None, batch=1, stride_a=0, stride_b=0, stride_c32=0, stride_c16=0,
               stride_res=0, splitk=0, workspace=None, stride_bias=0, drop_site_stride=0, a_patch=False,
-              fp8=False, scale_a=None, scale_b=None, stride_scale_a=0, stride_scale_b=0):
+              fp8=False, scale_a=None, scale_b=None, stride_scale_a=0, stride_scale_b=0,
+              norm=0, norm_w=None, norm_b=None, norm_eps=0.0, norm_y32=None, norm_y16=None, norm_mean=None,
+              norm_rstd=None, stride_norm_w=0, stride_norm_y=0, stride_norm_stat=0, norm_drop=None):
     """fp8: a / b are e4m3 byte tensors (lda, ldb, k, strides in bytes = elements) with fp32 row
-    scales scale_a [m] / scale_b [n] (vqa_gemm_desc.fp8)."""
+    scales scale_a [m] / scale_b [n] (vqa_gemm_desc.fp8).
+    norm: 1 LayerNorm / 2 RMSNorm of the c32 rows in the same launch (vqa_gemm_desc.norm);
+    `workspace` is then the zero-filled 64 KiB counter block (splitk_workspace); norm_drop a
+    lib.Dropout applied to y (RMSNorm)."""
     op_t = torch.uint8 if fp8 else torch.bfloat16
     for t in (a, b):
         assert not isinstance(t, torch.Tensor) or t.dtype == op_t, f"{op_t} operand expected"
@@ -64,6 +69,14 @@ def gemm_desc(a, b, m, n, k, *, lda, ldb, a_trans=False, b_trans=False, c32=None
     d.stride_bias, d.drop_site_stride = stride_bias, drop_site_stride
     d.fp8, d.scale_a, d.scale_b = int(fp8), addr(scale_a), addr(scale_b)
     d.stride_scale_a, d.stride_scale_b = stride_scale_a, stride_scale_b
+    for t in (norm_w, norm_b, norm_y32, norm_mean, norm_rstd):
+        assert not isinstance(t, torch.Tensor) or t.dtype == torch.float32, "fp32 tensor expected"
+    assert not isinstance(norm_y16, torch.Tensor) or norm_y16.dtype == torch.bfloat16, "bf16 tensor expected"
+    d.norm, d.norm_w, d.norm_b, d.norm_eps = int(norm), addr(norm_w), addr(norm_b), norm_eps
+    d.norm_y32, d.norm_y16, d.norm_mean, d.norm_rstd = addr(norm_y32), addr(norm_y16), addr(norm_mean), addr(norm_rstd)
+    d.stride_norm_w, d.stride_norm_y, d.stride_norm_stat = stride_norm_w, stride_norm_y, stride_norm_stat
+    if norm_drop is not None:
+        d.norm_drop = norm_drop
     set_splitk(d, splitk, workspace)
     return d
 
@@ -106,7 +119,7 @@ class Call:
 
 
 _PTR_FIELDS = {"GemmDesc": ("a", "b", "c32", "c16", "bias", "res32", "res16", "mask16", "workspace", "scale_a",
-                            "scale_b"),
+                            "scale_b", "norm_w", "norm_b", "norm_y32", "norm_y16", "norm_mean", "norm_rstd"),
                "AttnDesc": ("q", "k", "v", "o", "p", "bias", "key_mask", "dout", "dq", "dk", "dv", "dbias"),
                "AdamWDesc": ("param", "grad", "exp_avg", "exp_avg_sq", "max_exp_avg_sq", "param16", "state")}
 
@@ -125,9 +138,10 @@ def _pointers(call):
                 v = getattr(obj, f)
                 if v:
                     out.append((f"arg{i}.{f}", v))
-            drop = getattr(obj, "drop", None)
-            if drop is not None and drop.rng:
-                out.append((f"arg{i}.drop.rng", drop.rng))
+            for dn in ("drop", "norm_drop"):
+                drop = getattr(obj, dn, None)
+                if drop is not None and drop.rng:
+                    out.append((f"arg{i}.{dn}.rng", drop.rng))
     return out
 
 
