@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VQA_ABI_VERSION 19
+#define VQA_ABI_VERSION 20
 #define VQA_OK 0
 #define VQA_ERR_INVALID 1000
 
@@ -446,6 +446,52 @@ int vqa_head_bwd(const float* x, const float* att, const float* pooled, const fl
 int vqa_head_workspace_floats(int batch, int seq, int d, int answers);
 /* out[0] = (float) the number of targets >= 0 among targets[0..batch) (batch <= 1024). */
 int vqa_count_targets(const long long* targets, int batch, float* out, hipStream_t stream);
+
+/* ------------------------------------------------------------ evaluation ---
+ * The tail of the reference's valid_one_epoch / generate_answers flow (ABI 20): per-row
+ * top-k of the head's log-probs -- argmax / topk(exp(log-probs)), exp being monotonic
+ * (trainer/faster_rcnn_vqa_trainer.py:484-488, CNN_vqa_heatmap.py:75-87) -- and the epoch's
+ * loss average, accuracy and WUPS sums (:440-480), accumulated on the device so an epoch needs
+ * one host read.  fp32 log-probs exactly as vqa_head_fwd leaves them.
+ *
+ * Per-row outputs, written for all `batch` rows: topk_idx [batch, k] / topk_logp [batch, k] =
+ * the k largest log-probs of the row in descending order, equal values by ascending answer
+ * index (column 0 is the first-occurrence argmax); the values are the inputs' bits (callers
+ * take exp).  Entries are selected by (value, index) and marked taken, so a row holding -inf
+ * entries still yields every index once; with k > answers the slots past `answers` hold
+ * index -1 and -inf.  NaN inputs are unspecified.
+ *
+ * A row is valid if 0 <= targets[b] < answers; any other target (the engines' ignore_index
+ * padding, unlabelled rows), or targets == NULL, makes it ignored.  No target value causes an
+ * out-of-range read.
+ *
+ * acc (optional) -> one 64-byte block of eight 8-byte words that persists across calls:
+ *   int64 steps, rows, top1, topk, cursor; double loss_sum, nll_sum, sim_sum.
+ * With V = the call's valid rows in ascending row order, one call does: if V is not empty,
+ * steps += 1 and (loss given) loss_sum += (double)loss[0]; rows += |V|; for each row of V in
+ * order nll_sum += (double)nll[b] (nll given), sim_sum += (double)similarity[pred * answers +
+ * target] (similarity given; pred = column 0), top1 / topk count the rows whose target is
+ * column 0 / among the k columns, and (pred, target) go to pred_log[cursor] / tgt_log[cursor]
+ * while cursor < capacity; cursor advances either way (cursor > capacity afterwards: rows were
+ * dropped; nothing is written past capacity).  A call without a valid row leaves the block
+ * untouched.  The sums are one thread's sequential fp64 adds in that order -- no atomics -- so
+ * a host loop doing the same adds reproduces them bit for bit.
+ * Limits: batch <= 1024, answers <= 1024 (the head's), 1 <= k <= 16. */
+typedef struct vqa_eval_desc {
+  const float* logp;                  /* [batch, answers] */
+  const long long* targets;           /* [batch] or NULL */
+  const float* nll;                   /* [batch] vqa_head_fwd's per-row NLL, or NULL */
+  const float* loss;                  /* [1] vqa_head_fwd's batch-mean loss, or NULL */
+  const float* similarity;            /* [answers, answers], read at [prediction * answers + target], or NULL */
+  int batch, answers, k;
+  int* topk_idx;                      /* [batch, k] */
+  float* topk_logp;                   /* [batch, k] */
+  void* acc;                          /* the accumulator block (8-byte aligned), or NULL */
+  int* pred_log; int* tgt_log;        /* [capacity] each; may be NULL when capacity is 0 */
+  long long capacity;
+} vqa_eval_desc;
+
+int vqa_eval_rows(const vqa_eval_desc* d, hipStream_t stream);
 
 /* ------------------------------------------------------------- optimiser ---
  * clip_grad_norm_(1.0) + AdamW(amsgrad) + linear warmup/decay schedule

@@ -14,12 +14,13 @@ Layout:
   dp.py          the data-parallel (RCCL over xGMI) step
   data.py        the collate's image path on the GPU (resize + ToTensor)
   synthetic.py   deterministic weights / batches (no network)
+  metrics.py     host helpers of the evaluation path (the WUPS similarity table)
 """
 import importlib
 
 from . import synthetic  # noqa: F401  (numpy only)
 
-_LAZY = ("lib", "ops", "engine", "layout", "model", "trainer", "dp", "data", "vit_model", "vit_engine")
+_LAZY = ("lib", "ops", "engine", "layout", "model", "trainer", "dp", "data", "vit_model", "vit_engine", "metrics")
 
 
 def __getattr__(name):

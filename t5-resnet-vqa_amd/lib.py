@@ -114,6 +114,21 @@ class AdamWDesc(ctypes.Structure):
     ]
 
 
+class EvalDesc(ctypes.Structure):
+    """vqa_eval_desc: top-k of the head's log-probs + the epoch's metric accumulators."""
+    _fields_ = [
+        ("logp", c_void_p), ("targets", c_void_p), ("nll", c_void_p), ("loss", c_void_p), ("similarity", c_void_p),
+        ("batch", c_int), ("answers", c_int), ("k", c_int),
+        ("topk_idx", c_void_p), ("topk_logp", c_void_p), ("acc", c_void_p),
+        ("pred_log", c_void_p), ("tgt_log", c_void_p), ("capacity", c_ll),
+    ]
+
+
+EVAL_MAX_K = 16
+# the accumulator block's eight 8-byte words: five int64, then three fp64
+EVAL_ACC_INTS = ("steps", "rows", "top1", "topk", "cursor")
+EVAL_ACC_F64 = ("loss_sum", "nll_sum", "sim_sum")
+
 _lib = None
 
 
@@ -151,6 +166,7 @@ def load():
     lib.vqa_attn_path.argtypes = [ctypes.POINTER(AttnDesc), c_int]
     lib.vqa_attn_probs.argtypes = [ctypes.POINTER(AttnDesc), c_void_p]
     lib.vqa_adamw_amsgrad.argtypes = [ctypes.POINTER(AdamWDesc), c_void_p]
+    lib.vqa_eval_rows.argtypes = [ctypes.POINTER(EvalDesc), c_void_p]
     lib.vqa_adamw_rows.argtypes = [ctypes.POINTER(AdamWDesc), c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
     for name in ("vqa_norm_bwd_workspace_floats", "vqa_colsum_workspace_floats"):
         getattr(lib, name).argtypes = [c_int, c_int]

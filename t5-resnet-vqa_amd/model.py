@@ -206,6 +206,26 @@ class ResnetVQAModel:
         """faster_rcnn_vqa_trainer.py:484-488: argmax of exp(log-probs) over the answers."""
         return torch.argmax(torch.exp(lm_logits), dim=1)
 
+    def predict(self, question_input_ids, question_attention_masks, image_tensors, annotation_ids=None, topk=5):
+        """The `topk` most probable answers of every row, most probable first (equal
+        log-probs by ascending answer index, so column 0 is the argmax the reference takes,
+        faster_rcnn_vqa_trainer.py:484-488; its heat-map script's topk(exp(log-probs), 5),
+        CNN_vqa_heatmap.py:75-87): (indices [n, topk] int64, log_probs [n, topk] fp32) for the n
+        real rows; take exp for probabilities.  Runs the evaluation graph (captured on first
+        use, engine.eval_capture): eval mode, no dropout draw, a short batch padded as in
+        load_batch.  Rows with an annotation id also add to the engine's evaluation
+        accumulators (engine.eval_result)."""
+        self.load_batch(question_input_ids, question_attention_masks, image_tensors, annotation_ids)
+        e = self.engine
+        if e.eval_call is None:
+            e.eval_plan(topk)
+        elif e.eval_k != int(topk):                        # another k: re-plan, keeping table and capacity
+            e.eval_plan(topk, e.EVAL_SIM, e.eval_capacity)
+        if e.eval_graph is None:
+            e.eval_capture_graph()
+        e.eval_step()
+        return e.TOPK_IDX[:e.rows].long(), e.TOPK_LOGP[:e.rows].clone()
+
     # ------------------------------------------------------------------ weights
     def state_dict(self):
         """Reference keys -> fp32 CPU tensors (loadable by the reference ResnetVQAModel)."""

@@ -121,6 +121,8 @@ class Call:
 _PTR_FIELDS = {"GemmDesc": ("a", "b", "c32", "c16", "bias", "res32", "res16", "mask16", "workspace", "scale_a",
                             "scale_b", "norm_w", "norm_b", "norm_y32", "norm_y16", "norm_mean", "norm_rstd"),
                "AttnDesc": ("q", "k", "v", "o", "p", "bias", "key_mask", "dout", "dq", "dk", "dv", "dbias"),
+               "EvalDesc": ("logp", "targets", "nll", "loss", "similarity", "topk_idx", "topk_logp", "acc", "pred_log",
+                            "tgt_log"),
                "AdamWDesc": ("param", "grad", "exp_avg", "exp_avg_sq", "max_exp_avg_sq", "param16", "state")}
 
 

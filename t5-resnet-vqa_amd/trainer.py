@@ -16,8 +16,12 @@ Mirrors:
                     every 10% of the epoch                        :314-360
   valid_one_step    eval-mode forward (dropout off), no update    :408-430
   valid_one_epoch   the validation loop: average loss and exp/argmax
-                    predictions vs targets (WUPS needs nltk's WordNet, not
-                    on this path: accuracy is reported instead)   :408-480
+                    predictions vs targets, eager, with accuracy  :408-480
+  evaluate          the same epoch as one replayed forward-only graph per
+                    batch with top-k, accuracy and WUPS accumulated on the
+                    device (WUPS from a precomputed answers x answers table,
+                    metrics.similarity_table: nltk's WordNet is only needed
+                    where that table is made)                     :408-480
   convert_logits_to_predictions  argmax(exp(log-probs))            :484-488
 The whole train step is one replayed hipGraph; the only host sync per step is
 the `loss.item()` the reference API returns (pass sync=False to skip it).
@@ -40,6 +44,7 @@ import torch
 
 from . import dp
 from . import synthetic as S
+from .metrics import similarity_table  # noqa: F401  (the WUPS table `evaluate` takes)
 from .model import ResnetVQAModel
 
 HARD_CODED_LR = 5e-4          # faster_rcnn_vqa_trainer.py:244-261
@@ -172,6 +177,50 @@ class VQATrainer:
         t = torch.cat([x.cpu() for x in targets]) if targets else torch.zeros(0, dtype=torch.long)
         acc = float((p == t).float().mean()) if len(t) else 0.0
         return {"avg_loss": total / max(1, n), "predictions": p.tolist(), "targets": t.tolist(), "accuracy": acc}
+
+    def evaluate(self, batches, topk=5, similarity=None, use_graph=True):
+        """The reference's validation epoch (faster_rcnn_vqa_trainer.py:408-480) on the device:
+        every batch runs the forward-only evaluation graph (engine.eval_capture; eval mode, no
+        dropout draw, so the training run's masks do not depend on whether it validates), whose
+        vqa_eval_rows tail takes the top-k answers and adds to the epoch's accumulators; the
+        host reads them once, after the last batch.  Returns
+          avg_loss       mean of the per-batch mean losses (the reference's figure, :456)
+          sample_loss    mean NLL over the labelled rows (nll_sum / rows)
+          accuracy, topk_accuracy   target == the top answer / among the `topk` answers
+          wups           mean of similarity[prediction, target] (metrics.similarity_table: the
+                         reference's model-selection score), None without a table
+          predictions, targets      of the labelled rows, in order
+          steps, rows    batches with a labelled row, labelled rows
+        Rows without a valid annotation id (padding, unlabelled) count nowhere.  The model's
+        train / eval mode is restored.  use_graph=False issues the same calls eagerly
+        (debugging, A/B).  Data parallel: each rank evaluates the batches it is given and returns
+        its own figures; no collective runs here."""
+        from .metrics import check_similarity
+        m = self.model
+        sim = check_similarity(similarity, int(m.answer_spaces))    # before any device work
+        e = m.engine
+        if not hasattr(e, "eval_prepare"):
+            raise NotImplementedError("evaluate: the evaluation graph is planned for ResnetVQAModel's engine; "
+                                      "use valid_one_epoch for this model")
+        was = m.training
+        m.eval()
+        try:
+            e.eval_prepare(topk, sim, graph=use_graph)
+            e.eval_reset()
+            for data_items in batches:
+                m.load_items(data_items)
+                e.eval_step(use_graph=use_graph)
+            r = e.eval_result()
+        finally:
+            m.train(was)
+        if r["cursor"] > e.eval_capacity and self.logger:
+            self.logger(f"evaluate: {r['cursor'] - e.eval_capacity} rows past the log capacity "
+                        f"{e.eval_capacity} are counted but not listed in predictions / targets")
+        rows, steps = r["rows"], r["steps"]
+        return {"avg_loss": r["loss_sum"] / max(1, steps), "sample_loss": r["nll_sum"] / max(1, rows),
+                "accuracy": r["top1"] / max(1, rows), "topk_accuracy": r["topk"] / max(1, rows),
+                "wups": (r["sim_sum"] / max(1, rows)) if sim is not None else None,
+                "predictions": r["predictions"], "targets": r["targets"], "steps": steps, "rows": rows}
 
     # ------------------------------------------------------------------ optimizer checkpoints
     # The reference saves {'epoch', 'scheduler', 'optimizer'} with torch.save (callbacks.py:118-125)
