@@ -5,8 +5,14 @@ of shiv-vignesh/T5-Resnet-VQA (`model/resnet_vqa_model.py`,
 Layout:
   csrc/          hand-written HIP kernels + the extern "C" ABI (libvqa_hip.so)
   lib.py         ctypes binding of that ABI (fails loudly when the .so is absent)
-  engine.py      flat parameter/gradient/optimizer arenas, the explicit
+  engine_base.py what both engines share: the flat parameter/gradient/optimizer
+                 arenas, the prepared-call builders, the AdamW descriptors, the
+                 state-dict / optimizer-state readouts
+  engine.py      VQAEngine: the ResNet + T5-encoder + SGA plan, its explicit
                  forward/backward schedule, fused clip+AdamW, hipGraph capture
+  vit_engine.py  VitVQAEngine: the ViT + T5 encoder-decoder plan (config 4)
+  vit_model.py   its specs, layout and synthetic weights / batches
+  tune.py        the GEMM tuner (tile config + split-K per prepared GEMM)
   layout.py      the flat arena <-> reference state_dict mapping
   ops.py         prepared C-ABI calls (descriptors built once, replayed)
   model.py       mirror of the reference module API (ResnetVQAModel)
@@ -20,7 +26,8 @@ import importlib
 
 from . import synthetic  # noqa: F401  (numpy only)
 
-_LAZY = ("lib", "ops", "engine", "layout", "model", "trainer", "dp", "data", "vit_model", "vit_engine", "metrics")
+_LAZY = ("lib", "ops", "tune", "engine_base", "engine", "layout", "model", "trainer", "dp", "data", "vit_model",
+         "vit_engine", "metrics")
 
 
 def __getattr__(name):

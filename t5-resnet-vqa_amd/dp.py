@@ -29,7 +29,7 @@ import torch
 from . import lib as L
 from . import ops
 from . import synthetic as S
-from .engine import no_gc_capture
+from .engine_base import _after, no_gc_capture
 
 
 # T5 weight-gradient groups of a DP engine (VQAEngine t5_dw_group), top layer first: the
@@ -74,15 +74,6 @@ def plan_shards(buckets, world, align=64):
         chunk = (b - a) // (world * align) * align
         out.append((a, chunk, b))
     return out
-
-
-def _after(stream, other):
-    """`stream` waits for everything issued so far on `other` (an event, no host sync)."""
-    if stream is other:
-        return
-    ev = torch.cuda.Event()
-    ev.record(other)
-    stream.wait_event(ev)
 
 
 def _wait_only(w):

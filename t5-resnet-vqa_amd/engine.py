@@ -24,12 +24,17 @@ Design (MI355X-first, not a translation of eager PyTorch):
     applied inside the producing kernels from a stateless counter hash
     (include/vqa_hip.h "dropout"); the backward regenerates the masks, nothing
     is stored.  dropout=0 gives eval-mode numerics (golden-vector parity).
+
+This module holds what is the ResNet engine's own: the frozen-ResNet plan, the T5-encoder /
+SGA / head forward and backward plans (fused norms, fp8, batched weight gradients), the
+deferred and row-split optimizer plan, the stream schedule of the step, graph capture and
+the evaluation graph.  The arenas, the call builders, the AdamW descriptors and the
+state-dict / optimizer-state readouts are engine_base.EngineBase's, shared with
+vit_engine.VitVQAEngine; the GEMM tuner is tune.py.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes
-import gc
 import os
 import math
 
@@ -39,17 +44,9 @@ import torch
 from . import lib as L
 from . import ops
 from . import synthetic as S
+from .engine_base import (BF16, F32, I64, IGNORE_INDEX, SITE_EMBED, SITE_FINAL, EngineBase, _after,  # noqa: F401
+                          _check_attn_path, _h2d, _Seq, batch_rows, load_rows, no_gc_capture, t5_site)
 from .layout import ParamLayout, fold_bn, t5_bucket_map
-
-BF16, F32, I64 = torch.bfloat16, torch.float32, torch.int64
-
-# dropout site ids (the hash key of each nn.Dropout application of the step)
-SITE_EMBED, SITE_FINAL = 1, 2                  # T5Stack: dropout(inputs_embeds) :725, dropout(final_ln) :745
-
-
-def t5_site(layer, kind):
-    """kind 0 attention probs (:168), 1 attention residual branch (:400), 2 FF inner (:86), 3 FF residual (:140)"""
-    return 16 + 4 * layer + kind
 
 
 def sga_site(block, kind):
@@ -69,134 +66,29 @@ def stem_s2d_weight(wf):
     return np.concatenate([w, np.zeros((co, 4, 4, 16 - 4 * ci), np.float32)], 3)
 
 
-_TUNE_CACHE = {}
-_TUNE_CACHE_COLD = {}            # autotune(cold=True): choices timed from cold caches
-SPLITS = (1, 2, 3, 4, 6, 8)        # split-K counts the tuner tries for small grids
-
-
-def lib_gemm_configs():
-    import re
-    return int(re.search(r"#define VQA_GEMM_CONFIGS (\d+)", open(L.HEADER).read()).group(1))
-
-
-def _gemm_key(d):
-    geo = lambda g: (g.n, g.h, g.w, g.c, g.oh, g.ow, g.kh, g.kw, g.stride, g.pad)
-    return (d.m, d.n, d.k, d.batch, d.a_trans, d.b_trans, d.a_conv, d.b_conv,
-            geo(d.ga) if d.a_conv else None, geo(d.gb) if d.b_conv else None,
-            bool(d.c32), bool(d.c16), bool(d.bias), bool(d.res32), bool(d.res16), bool(d.mask16), d.relu,
-            d.beta != 0.0, d.drop.p > 0.0) + (("fp8",) if d.fp8 else ()) + (("norm", d.norm) if d.norm else ())
-
-
-class _Seq:
-    """Several prepared calls issued as one (a deferred AdamW range and the e4m3 weight
-    copies that follow it)."""
-    def __init__(self, calls):
-        self.calls = calls
-
-    def __call__(self, stream):
-        for c in self.calls:
-            c(stream)
-
-
-@contextlib.contextmanager
-def no_gc_capture():
-    """Stream capture with the cyclic garbage collector held off.  Engines (and the graphs /
-    tensors they own) are reclaimed through reference cycles; a collection that lands inside
-    a capture destroys another engine's graph execs and frees its blocks while the capture
-    is being recorded (measured: the later replay of the captured graph crashed in the
-    runtime).  Collect first, then keep the collector off until the capture has ended."""
-    was = gc.isenabled()
-    gc.collect()
-    gc.disable()
-    try:
-        yield
-    finally:
-        if was:
-            gc.enable()
-
-
-_WARNED_ATTN = set()
-
-
-def _check_attn_path(d, fn):
-    """Say it loudly (once per shape) when a planned attention call would run the scalar VALU
-    kernel (include/vqa_hip.h vqa_attn_path): it is correct but an order of magnitude slower
-    than the MFMA kernels, which cover lq <= 32, lk <= 160 (key mask: lk <= 64)."""
-    path = L.load().vqa_attn_path(ctypes.byref(d), int(fn == "vqa_attn_bwd"))
-    if path == L.ATTN_VALU:
-        key = (fn, d.lq, d.lk, d.dh, bool(d.key_mask))
-        if key not in _WARNED_ATTN:
-            _WARNED_ATTN.add(key)
-            import warnings
-            warnings.warn(f"{fn}: lq={d.lq} lk={d.lk} dh={d.dh} key_mask={bool(d.key_mask)} runs the scalar VALU "
-                          "attention kernel (no MFMA kernel covers this shape)", RuntimeWarning, stacklevel=3)
-    return path
-
-
-def _h2d(dst, src):
-    """dst <- src (numpy / torch, host or device).  Asynchronous only from device or pinned
-    memory: an async copy out of a pageable temporary (freed when this returns) may be read
-    by the runtime after the free."""
-    src = torch.as_tensor(src).to(dst.dtype).reshape(dst.shape)
-    dst.copy_(src, non_blocking=src.is_cuda or src.is_pinned())
-
-
-IGNORE_INDEX = -100          # nn.NLLLoss's default ignore_index: the head skips rows with a target < 0
-
-
-def batch_rows(batch, key, planned, allow_empty=False):
-    """Rows of a collate batch (the reference's loaders have no drop_last, so an epoch's last
-    batch is short: faster_rcnn_vqa_trainer.py:172-197); 1 <= rows <= the planned batch (0 rows
-    only for a data-parallel rank whose share of the global batch is empty: allow_empty)."""
-    n = int(torch.as_tensor(batch[key]).shape[0])
-    if not (0 if allow_empty else 1) <= n <= planned:
-        lo = 0 if allow_empty else 1
-        raise ValueError(f"{key}: batch of {n} rows; this engine is planned for {lo}..{planned} rows")
-    return n
-
-
-def load_rows(dst, src, n, fill=None, empty_fill=0):
-    """dst[:n] <- src (n rows); the planned rows past n are padding: copies of rows 0..n-1
-    (real samples, so every activation stays finite) or `fill` (targets: IGNORE_INDEX, so the
-    padded rows add nothing to the loss or to any gradient -- the NLL mean runs over the n
-    real rows).  n = 0 (an empty data-parallel rank): every row is `fill`, else `empty_fill`
-    (finite inputs whose targets are all ignored: the rank's gradient is exactly zero)."""
-    if src is None:
-        return
-    B = dst.shape[0]
-    if n == 0:
-        dst.fill_(fill if fill is not None else empty_fill)
-        return
-    _h2d(dst[:n] if n < B else dst, src)
-    if n == B:
-        return
-    if fill is not None:
-        dst[n:].fill_(fill)
-        return
-    i = n
-    while i < B:                                   # doubling copies of the real rows
-        k = min(i, B - i)
-        dst[i:i + k].copy_(dst[:k])
-        i += k
-
-
-class VQAEngine:
+class VQAEngine(EngineBase):
     def __init__(self, state_dict, vision="resnet50", batch=64, seq_len=32, image_size=224, device="cuda:0",
                  warmup=10, total=100, num_blocks=3, answer_spaces=170, grad_scale=1.0, max_norm=1.0,
                  betas=(0.9, 0.999), eps=1e-8, weight_decay=0.1, dropout=0.1, seed=0, pipeline=False,
                  t5_dw_group=None, defer_optimizer=True, dw_stream=None, sga_dw_batch=True, pair_bwd=True,
                  language_model="t5-base", fp8=False, sga_attn_group=True, fuse_norm=None):
-        L.load()
+        super().__init__(device, dropout, seed, warmup, total, max_norm, betas, eps, weight_decay, grad_scale)
         # fuse_norm: every forward LayerNorm / RMSNorm but layer 0's ln0 runs as the tail of the
         # GEMM that writes its input (vqa_gemm_desc.norm) instead of as a launch of its own;
-        # same bits.  Opt-in; None reads the environment (VQA_FUSE_NORM=1), like VQA_STEM.
+        # same bits.  Opt-in; None reads the environment (VQA_FUSE_NORM=1).
         self.fuse_norm = (os.environ.get("VQA_FUSE_NORM", "0") == "1") if fuse_norm is None else bool(fuse_norm)
         self.fuse_norm_kept = []          # norms left stand-alone although fuse_norm is on, with the reason
         # pipeline: the frozen ResNet (no trainable input) of the NEXT batch runs on its own
         # stream beside this step's T5 / SGA / backward / optimizer (see train_step)
         self.pipeline = bool(pipeline)
-        self.p_drop, self.seed = float(dropout), int(seed)
-        self.dev = torch.device(device)
+        # where the pipelined step issues the next batch's ResNet (_step_pipelined: first | last |
+        # interleave | root; bench.py sets both), and how many of its calls lead an interleave
+        self.res_order, self.res_head = "first", 4
+        self._res_feed = None             # res_order "interleave": [calls left, stream handle] while a step is issued
+        self._keep_graph = False          # capture(keep_graph=True): the hipGraph_t of each part is kept
+        self._rstream_handle = None       # set_res_cumask: the CU-masked ResNet stream ...
+        self._rstream_plain = None        # ... and the engine's own, put back by reset_res_cumask
+        self.EMB_MARK = None              # row marks of the split embedding update (_plan_optimizer)
         self.vision, self.B, self.L, self.H = vision, batch, seq_len, image_size
         assert image_size % 2 == 0, "the space-to-depth stem needs an even image size"
         self.NB, self.A = num_blocks, answer_spaces
@@ -216,10 +108,6 @@ class VQAEngine:
             raise ValueError(f"answer_spaces={answer_spaces}: the fused answer head supports 1..1024 answers")
         if not 1 <= seq_len <= 64:
             raise ValueError(f"seq_len={seq_len}: the attention / pooler kernels support 1..64 question tokens")
-        self.warmup, self.total, self.max_norm = warmup, total, max_norm
-        self.betas, self.eps, self.wd = betas, eps, weight_decay
-        self.grad_scale = grad_scale
-        self.group_lr = {}                # per-group LR overrides (trainer optimizer_kwargs)
         # dX + dW of a layer as one paired GEMM launch (pair_bwd=False: separate launches)
         self.pair_bwd = bool(pair_bwd)
         # T5 weight gradients: per weight ONE launch batched over a group of layers (the
@@ -264,9 +152,7 @@ class VQAEngine:
             self._plan_backward()
             self._plan_optimizer()
             self._run(self.quant_all)                     # e4m3 weights of the initial parameters
-        self.graph = None
-        self.eval_graph = None           # the forward-only evaluation graph (eval_capture)
-        self.eval_call = None            # its vqa_eval_rows tail (eval_plan)
+        self.eval_call = None            # the evaluation graph's vqa_eval_rows tail (eval_plan)
         self.allreduce = None            # set by the DP trainer: fn(G32 tensor) on the current stream
         self._side = torch.cuda.Stream(self.dev)
         self._wside = torch.cuda.Stream(self.dev)
@@ -275,43 +161,24 @@ class VQAEngine:
         self.allow_empty_rows = False     # use_global_rows (DP): a rank may get 0 rows
         self._img_rows_next = None        # pipelined: rows of the images whose features the next batch uses
         self.count_call = None
-        self._scratch = None             # split-K workspace used while autotuning
 
     @classmethod
     def from_state_dict(cls, sd, **kw):
         return cls(sd, **kw)
 
     # ------------------------------------------------------------------ allocation
-    def _t(self, shape, dtype=F32, zero=False):
-        f = torch.zeros if zero else torch.empty
-        return f(shape, dtype=dtype, device=self.dev)
-
     def _alloc_params(self, sd):
-        lay = self.lay
-        flat = lay.pack(sd)
-        self.P32 = torch.from_numpy(flat).to(self.dev)
-        self.P16 = self.P32.to(BF16)
-        self.G32 = self._t(lay.total, zero=True)
+        self._alloc_arenas(sd)
+        self.bucket = torch.from_numpy(t5_bucket_map(self.L, self.L)).reshape(-1).to(self.dev)
+
+    def _alloc_shadow_arenas(self):
         if self.fp8:
             # e4m3 weight shadow and its row scales, at the fp32 arena's element offsets: row r of
             # segment s is W8[s.offset + r*K :] with scale WSC[s.offset + r] (constant strides
             # between the blocks' segments, as the batched launches need)
-            self.W8 = torch.empty(lay.total, dtype=torch.uint8, device=self.dev)
-            self.WSC = torch.ones(lay.total, dtype=F32, device=self.dev)
+            self.W8 = torch.empty(self.lay.total, dtype=torch.uint8, device=self.dev)
+            self.WSC = torch.ones(self.lay.total, dtype=F32, device=self.dev)
             self._xq = {}
-        self.M = self._t(lay.total, zero=True)
-        self.V = self._t(lay.total, zero=True)
-        self.VMAX = self._t(lay.total, zero=True)
-        self.p32, self.p16, self.g32 = {}, {}, {}
-        for s in lay.segments.values():
-            sl = slice(s.offset, s.offset + s.numel)
-            self.p32[s.name] = self.P32[sl].view(s.shape)
-            self.p16[s.name] = self.P16[sl].view(s.shape)
-            self.g32[s.name] = self.G32[sl].view(s.shape)
-        self.opt_state = self._t(L.ST_FLOATS, zero=True)
-        # dropout RNG state {seed, counter, training}; the forward's first call advances the counter
-        self.RNG = torch.from_numpy(np.array([self.seed & 0xFFFFFFFF, 0, 1, 0], np.uint32).view(np.int32)).to(self.dev)
-        self.bucket = torch.from_numpy(t5_bucket_map(self.L, self.L)).reshape(-1).to(self.dev)
 
     def _plan_resnet(self, sd):
         """Frozen torchvision ResNet (eval BN folded) as a list of implicit-GEMM convs."""
@@ -369,34 +236,21 @@ class VQAEngine:
         # (as a 4x4 stride-1 conv over the space-to-depth image: K 256 instead of 7*7*8 = 392)
         w16, b32 = conv_w("conv1", "bn1", s2d=True)
         g = ops.conv_geom(B, hz, hz, 16, h1, h1, 4, 4, 1, 1)
-        stem = os.environ.get("VQA_STEM", "img")            # img | pool | patch | gemm (A/B switches)
-        fused_img = stem == "img" and H % 32 == 0 and hz == h1 + 1 and h2 == h1 // 2
-        # the space-to-depth image only exists for the forms that read it (B x 113 x 113 x 16 bf16)
+        # the shape alone chooses the form: the fused kernel's tiles need H % 32 == 0 (then, H being
+        # even, hz == h1 + 1 and h2 == h1 // 2 hold too)
+        fused_img = H % 32 == 0
+        # the space-to-depth image only exists for the form that reads it (B x hz x hz x 16 bf16)
         self.IMG8 = None if fused_img else self._t((B, hz, hz, 16), BF16)
         if fused_img:
             # space-to-depth + stem + maxpool in one pass (csrc/stem.hip): patches staged from the
             # fp32 image, only the pooled map written; bit-identical to the three-kernel form below
             self.res_calls.append(ops.Call("vqa_stem_pool_img", self.IMG.data_ptr(), w16.data_ptr(), b32.data_ptr(),
                                            bufs[1].data_ptr(), B, H, keep=(self.IMG, w16, b32, bufs[1])))
-            stem = None
         else:
             self.res_calls.append(ops.Call("vqa_image_to_s2d16", self.IMG.data_ptr(), self.IMG8.data_ptr(), B, H, H,
                                            keep=(self.IMG, self.IMG8)))
-        if stem is None:
-            pass
-        elif stem in ("img", "pool") and h1 % 16 == 0 and hz == h1 + 1 and h2 == h1 // 2:
-            # stem + maxpool in one pass from LDS input patches (csrc/stem.hip): only the pooled
-            # map is written; bit-identical to the implicit GEMM + vqa_maxpool3x3s2_nhwc below
-            self.res_calls.append(ops.Call("vqa_stem_pool_s2d", self.IMG8.data_ptr(), w16.data_ptr(), b32.data_ptr(),
-                                           bufs[1].data_ptr(), B, hz, h1, keep=(self.IMG8, w16, b32, bufs[1])))
-        else:
-            if stem in ("pool", "patch") and h1 % 16 == 0 and hz == h1 + 1:
-                self.res_calls.append(ops.Call("vqa_stem_s2d_conv", self.IMG8.data_ptr(), w16.data_ptr(),
-                                               b32.data_ptr(), bufs[0].data_ptr(), B, hz, h1,
-                                               keep=(self.IMG8, w16, b32, bufs[0])))
-            else:
-                self._gemm(self.res_calls, self.IMG8, w16, B * h1 * h1, 64, 256, lda=256, ldb=256, ga=g,
-                           c16=bufs[0], ldc16=64, bias=b32, relu=True)
+            self._gemm(self.res_calls, self.IMG8, w16, B * h1 * h1, 64, 256, lda=256, ldb=256, ga=g,
+                       c16=bufs[0], ldc16=64, bias=b32, relu=True)
             self.res_calls.append(ops.Call("vqa_maxpool3x3s2_nhwc", bufs[0].data_ptr(), bufs[1].data_ptr(), B, h1,
                                            h1, 64, h2, h2, keep=(bufs[0], bufs[1])))
         x = bufs[1]
@@ -407,8 +261,7 @@ class VQAEngine:
             t1, t2, ds, y = free[0], free[1], free[2], free[3]
             if idx == nblocks_total - 1:
                 y = self.F4N
-            fuse = bottleneck and (vm + p + "downsample.0.weight") in sd and os.environ.get("VQA_RES_FUSE_DS", "1") != "0"
-            if fuse:
+            if bottleneck and (vm + p + "downsample.0.weight") in sd:
                 # conv3 and the 1x1 downsample as ONE GEMM over the concatenated K (r05):
                 # [conv2 out | x subsampled] . [W3 | Wd]^T + (b3 + bd), ReLU -- conv2 writes the
                 # first `planes` columns of the `ds` buffer, vqa_subsample_nhwc the other `ci`;
@@ -561,15 +414,7 @@ class VQAEngine:
         self.SQ_PARTS = 1024                              # per sqnorm range (three ranges, §3.7)
         self.WS_SQ = t(3 * self.SQ_PARTS, torch.float64)
 
-    # ------------------------------------------------------------------ call helpers
-    # Every helper records the tensors it bakes into a call (ops.Call.keep), so no
-    # buffer can be freed while a prepared call still points at it.  Raw int
-    # addresses (sub-views made with ops.addr) must come from tensors that are
-    # passed too or are engine attributes.
-    def _gemm(self, lst, a, b, m, n, k, keep=(), **kw):
-        ts = [a, b] + [v for v in kw.values() if isinstance(v, torch.Tensor)] + list(keep)
-        lst.append(ops.gemm_call(ops.gemm_desc(a, b, m, n, k, **kw), [t for t in ts if isinstance(t, torch.Tensor)]))
-
+    # ------------------------------------------------------------------ call helpers (beside EngineBase's)
     def _sga_self_keep(self):
         """The flat-arena views the batched SGA self-attention launches read past: the
         blocks' q|k|v and merge weights, biases and gradients sit side by side (layout.py)."""
@@ -589,48 +434,6 @@ class VQAEngine:
             return dict(groups=1)
         return dict(groups=self.NB, gstride_qkv=3 * D, gstride_o=T * D, gstride_dout=T * D,
                     gstride_p=self.P1A[0].numel(), gdrop_site_stride=sga_site(1, 0) - sga_site(0, 0))
-
-    def _set_drop(self, call, site):
-        d = self._drop(site)
-        if d is not None:
-            call.desc.drop = d
-            call.keep = call.keep + (self.RNG,)
-
-    def _call(self, lst, name, *args, extra=()):
-        ts = tuple(a for a in args if isinstance(a, torch.Tensor)) + tuple(extra)
-        lst.append(ops.Call(name, *[ops.addr(a) if isinstance(a, torch.Tensor) else a for a in args], keep=ts))
-
-    def _attn(self, lst, fn, drop=None, keep=(), **kw):
-        d = L.AttnDesc()
-        for k, v in kw.items():
-            setattr(d, k, ops.addr(v) if isinstance(v, torch.Tensor) else v)
-        ts = tuple(v for v in kw.values() if isinstance(v, torch.Tensor)) + tuple(keep)
-        dd = self._drop(drop) if drop is not None else None
-        if dd is not None:
-            d.drop = dd
-            ts = ts + (self.RNG,)
-        _check_attn_path(d, fn)
-        lst.append(ops.Call(fn, ctypes.byref(d), keep=ts, desc=d))
-
-    def _drop(self, site):
-        """vqa_dropout for `site` (None when dropout is off)."""
-        if self.p_drop <= 0.0:
-            return None
-        return L.Dropout(self.p_drop, site, self.RNG.data_ptr())
-
-    def _dptr(self, site, keep):
-        """`const vqa_dropout*` argument (0 = none); the struct is kept alive through `keep`."""
-        d = self._drop(site)
-        if d is None:
-            return None
-        keep.append(d)
-        return ctypes.addressof(d)
-
-    @property
-    def drop_scale(self):
-        """1/(1-p) in fp32, the multiplier of a kept element (as the kernels compute it)."""
-        p = np.float32(self.p_drop)
-        return float(np.float32(1.0) / (np.float32(1.0) - p))
 
     # ------------------------------------------------------------------ fp8 (config 5)
     FP8_T5 = ("qkv_w", "o_w", "wi", "wo")
@@ -663,33 +466,6 @@ class VQAEngine:
         self._call(lst, "vqa_quant_rows_fp8", x16, 1, k, rows, k, x8, k, xs)
         return x8, xs
 
-    def _linear(self, lst, x16, wname, m, out32=None, out16=None, bias=True, relu=False, res32=None, drop=None,
-                norm=None):
-        """norm: vqa_gemm_desc norm fields (ops.gemm_desc keywords) of a row norm fused behind
-        this GEMM (fuse_norm), or None."""
-        nkw = dict(norm or {})
-        nkeep = tuple(nkw.pop("keep", ()))
-        if getattr(self, "fp8", False) and self._is_fp8(wname):          # (borrowed by VitVQAEngine: no fp8)
-            x8, xs = self._quant_act(lst, (wname, "x"), x16, m)
-            w8, ws = self._w8(wname)
-            n, k = w8.shape
-            self._gemm(lst, x8, w8, m, n, k, lda=k, ldb=k, c32=out32, ldc32=n, c16=out16, ldc16=n,
-                       bias=self.p32[wname[:-1] + "b"] if bias else None, relu=relu, res32=res32, ldres=n, fp8=True,
-                       scale_a=xs, scale_b=ws, keep=(self.W8, self.WSC) + nkeep, **nkw)
-            d = self._drop(drop) if drop is not None else None
-            if d is not None:
-                lst[-1].desc.drop = d
-                lst[-1].keep = lst[-1].keep + (self.RNG,)
-            return
-        w = self.p16[wname]
-        n, k = w.shape
-        self._gemm(lst, x16, w, m, n, k, lda=k, ldb=k, c32=out32, ldc32=n, c16=out16, ldc16=n,
-                   bias=self.p32[wname[:-1] + "b"] if bias else None, relu=relu, res32=res32, ldres=n, keep=nkeep, **nkw)
-        d = self._drop(drop) if drop is not None else None
-        if d is not None:
-            lst[-1].desc.drop = d
-            lst[-1].keep = lst[-1].keep + (self.RNG,)
-
     def _rms_kw(self, w, y16, rstd, ws, y32=None, drop=None):
         """ops.gemm_desc keywords of a T5 RMSNorm fused behind the GEMM that writes its input."""
         kw = dict(norm=L.NORM_RMS, norm_w=w, norm_eps=1e-6, norm_y32=y32, norm_y16=y16, norm_rstd=rstd, workspace=ws)
@@ -702,13 +478,6 @@ class VQAEngine:
         """... of an SGA LayerNorm."""
         return dict(norm=L.NORM_LAYER, norm_w=g, norm_b=b, norm_eps=1e-5, norm_y32=y32, norm_y16=y16, norm_mean=mean,
                     norm_rstd=rstd, workspace=ws, **strides)
-
-    def _dx(self, lst, dy16, wname, m, out32=None, out16=None, res32=None, mask16=None, beta=0.0, alpha=1.0):
-        """dX[m, k] = alpha * dY[m, n] W[n, k]  (+res) (*mask>0) (+beta*out32)"""
-        w = self.p16[wname]
-        n, k = w.shape
-        self._gemm(lst, dy16, w, m, k, n, lda=n, ldb=k, b_trans=True, c32=out32, ldc32=k, c16=out16, ldc16=k,
-                   res32=res32, ldres=k, mask16=mask16, ldmask=k, beta=beta, alpha=alpha)
 
     def _dxdw(self, lst, dy16, x16, wname, rows, bias_from=None, **dxkw):
         """A layer's input gradient and weight gradient (they share dY) as ONE paired
@@ -724,58 +493,11 @@ class VQAEngine:
                             desc=(gx.desc, gw.desc)))
         lst.extend(tmp[2:])
 
-    def _defer(self, ws, parts, stride, cols, out, beta=0.0, offset=0):
-        """Queue the final reduction out = beta*out + sum_p ws[offset + p*stride + c] (a norm
-        weight/bias or Linear bias gradient whose per-block partial rows a backward kernel
-        wrote); _flush() finishes every queued one in a single vqa_colsum_batched launch."""
-        self._jobs.append((ops.addr(ws) + 4 * offset, ops.addr(out), stride, parts, cols, beta, (ws, out)))
-
-    def _flush(self, lst):
-        if not self._jobs:
-            return
-        arr = (L.ColsumJob * len(self._jobs))()
-        blk = 0
-        keep = []
-        for j, (ws, out, stride, parts, cols, beta, k) in enumerate(self._jobs):
-            arr[j] = L.ColsumJob(ws, out, stride, parts, cols, beta, blk)
-            blk += -(-cols // 64)
-            keep += list(k)
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.dev)
-        lst.append(ops.Call("vqa_colsum_batched", raw.data_ptr(), len(self._jobs), blk, keep=tuple(keep) + (raw,)))
-        self._jobs = []
-
-    def _norm_ws(self):
-        """A private partial-row workspace for one deferred norm backward."""
-        D = self.D
-        return self._t(L.load().vqa_norm_bwd_workspace_floats(self.T, D))
-
     def _gbuf(self, name, shape):
         """A bf16 backward buffer private to one use (see _plan_backward)."""
         if name not in self._gbufs:
             self._gbufs[name] = self._t(shape, BF16)
         return self._gbufs[name]
-
-    def _bias_colsum(self, lst, dy16, rows, bname):
-        """A Linear bias gradient = column sums of its bf16 output gradient (deferred)."""
-        lib = L.load()
-        n = dy16.shape[-1]
-        ws = self._t(lib.vqa_colsum_workspace_floats(rows, n))
-        self._call(lst, "vqa_colsum", dy16, 1, rows, n, n, None, 0.0, ws)
-        self._defer(ws, lib.vqa_colsum_parts(rows), n, n, self.g32[bname])
-
-    def _dw(self, lst, dy16, x16, wname, rows, bias_from=None, bias_bf16=True):
-        """dW[n, k] = dY[rows, n]^T X[rows, k]; optional bias grad = colsum(dY).
-        Tagged `side`: nothing on the dX chain reads them, so the step graph runs
-        them on a third stream beside the chain (joined before the optimizer)."""
-        g = self.g32[wname]
-        n, k = g.shape
-        self._gemm(lst, dy16, x16, n, k, rows, lda=n, ldb=k, a_trans=True, b_trans=True, c32=g, ldc32=k)
-        lst[-1].side = True
-        if bias_from is not None:                   # partial column sums now, final sum deferred (_flush)
-            lib = L.load()
-            ws = self._t(lib.vqa_colsum_workspace_floats(rows, n))
-            self._call(lst, "vqa_colsum", bias_from, int(bias_bf16), rows, n, n, None, 0.0, ws)
-            self._defer(ws, lib.vqa_colsum_parts(rows), n, n, self.g32[wname[:-1] + "b"])
 
     # ------------------------------------------------------------------ forward plan
     def _plan_forward(self):
@@ -964,8 +686,6 @@ class VQAEngine:
         # a prefix of G32: DP all-reduces bucket [prev_end, end) as soon as it is final.
         self.ready_marks = []
         self._sq_split = None        # (call index, prefix end) where the grad-norm pass can start early
-
-        self._jobs = []
 
         def mark(seg):
             self._flush(b)                          # finish this segment's deferred reductions first
@@ -1210,22 +930,8 @@ class VQAEngine:
                    extra=[self.G32, self.WS_SQ])
         self._call(o, "vqa_optim_finalize", self.WS_SQ, 3 * K, float(self.grad_scale), float(self.max_norm),
                    int(self.warmup), int(self.total), float(self.betas[0]), float(self.betas[1]), self.opt_state)
-        d = L.AdamWDesc()
-        d.param, d.grad = self.P32.data_ptr(), self.G32.data_ptr()
-        d.exp_avg, d.exp_avg_sq, d.max_exp_avg_sq = self.M.data_ptr(), self.V.data_ptr(), self.VMAX.data_ptr()
-        d.param16 = self.P16.data_ptr()
-        d.n = n
-        ends, lrs = self.lay.group_of_element()
-        lrs = [self.group_lr.get(g, lr) for g, lr in zip(self.lay.groups, lrs)]
-        d.ngroups = len(ends)
-        for i, (e, lr) in enumerate(zip(ends, lrs)):
-            d.group_end[i], d.group_lr[i] = e, lr
-        d.beta1, d.beta2, d.eps, d.weight_decay = self.betas[0], self.betas[1], self.eps, self.wd
-        d.grad_scale = self.grad_scale
-        d.state = self.opt_state.data_ptr()
-        self._adam_desc = d
-        keep = (self.P32, self.G32, self.M, self.V, self.VMAX, self.P16, self.opt_state)
-        self.adam_full = ops.Call("vqa_adamw_amsgrad", ctypes.byref(d), desc=d, keep=keep)
+        self._adam_desc = self._adam_desc_full()
+        self.adam_full = self._adam_call(self._adam_desc)
         # Deferred update (defer_opt): step k's AdamW runs inside step k+1's forward, one
         # parameter range at a time on its own stream, each range just before its first use
         # (the forward reads the layout back to front: T5 layers 0..11, then the scaler / SGA /
@@ -1260,15 +966,7 @@ class VQAEngine:
         self.adam_segs = []
         self.adam_embed = None
         for name, lo, hi in cuts:
-            ds = L.AdamWDesc()
-            ctypes.memmove(ctypes.addressof(ds), ctypes.addressof(d), ctypes.sizeof(d))
-            ds.param, ds.grad = ops.addr(self.P32, lo), ops.addr(self.G32, lo)
-            ds.exp_avg, ds.exp_avg_sq = ops.addr(self.M, lo), ops.addr(self.V, lo)
-            ds.max_exp_avg_sq, ds.param16 = ops.addr(self.VMAX, lo), ops.addr(self.P16, lo)
-            ds.n = hi - lo
-            for i, e in enumerate(ends):
-                ds.group_end[i] = e - lo
-            c = ops.Call("vqa_adamw_amsgrad", ctypes.byref(ds), desc=ds, keep=keep)
+            c = self.adam_range_call(lo, hi)
             if quant[name]:
                 c = _Seq([c] + quant[name])
             if name == "embed":
@@ -1289,25 +987,17 @@ class VQAEngine:
         # keeps only the rel-bias range and the touched rows (tail_calls).  Bit-identical to the
         # dense range; used by the stream / graph step (run_backward_streams with sq_overlap),
         # while opt_calls keeps the dense form (eager steps, dp.DataParallelStep's finish graph).
-        self.embed_split = self.defer_opt and os.environ.get("VQA_EMBED_SPLIT", "1") != "0"
+        self.embed_split = self.defer_opt
         self.tail_calls = o[2:]
         self.emb_pre = []
         if self.embed_split:
             emb = lay["t5.embed"]
             assert emb.offset + emb.numel == n and self.adam_embed is o[-1]
-            if getattr(self, "EMB_MARK", None) is None:
+            if self.EMB_MARK is None:
                 self.EMB_MARK = torch.full((S.T5_VOCAB,), -1, dtype=torch.int32, device=self.dev)
-            dt = L.AdamWDesc()
-            ctypes.memmove(ctypes.addressof(dt), ctypes.addressof(d), ctypes.sizeof(d))
             lo = emb.offset
-            dt.param, dt.grad = ops.addr(self.P32, lo), ops.addr(self.G32, lo)
-            dt.exp_avg, dt.exp_avg_sq = ops.addr(self.M, lo), ops.addr(self.V, lo)
-            dt.max_exp_avg_sq, dt.param16 = ops.addr(self.VMAX, lo), ops.addr(self.P16, lo)
-            dt.n = emb.numel
-            for i in range(d.ngroups):                     # as adam_range_call: ends relative to the table
-                dt.group_end[i] = d.group_end[i] - lo
-            self._emb_desc = dt
-            keep = (self.P32, self.G32, self.M, self.V, self.VMAX, self.P16, self.opt_state, self.EMB_MARK)
+            self._emb_desc = dt = self._adam_range_desc(lo, n)       # the table's rows
+            keep = self._adam_keep() + (self.EMB_MARK,)
             rows_call = lambda touched: ops.Call("vqa_adamw_rows", ctypes.byref(dt), self.EMB_MARK.data_ptr(),  # noqa: E731
                                                  S.T5_VOCAB, self.D, touched, int(self.warmup), int(self.total),
                                                  desc=dt, keep=keep)
@@ -1317,54 +1007,17 @@ class VQAEngine:
                             # the untouched rows' pass as 256 workgroups striding over the rows: a
                             # 32k-block grid beside the chain cost what it saved at the tail (A/B:
                             # 6.47-6.48 ms either way), 256 measured 6.44-6.47
-                            rows_call(int(os.environ.get("VQA_EMB_GRID", "256")))]
+                            rows_call(256)]
             self.tail_calls = o[2:-1] + [self.adam_range_call(lay["t5.relbias"].offset, lo), rows_call(1)]
 
-    def adam_range_call(self, lo, hi):
-        """The fused AdamW-amsgrad pass over flat parameters [lo, hi) only (the step's device
-        state: clip coefficient, schedule, bias corrections; no-op unless an update is pending)."""
-        d = self._adam_desc
-        ds = L.AdamWDesc()
-        ctypes.memmove(ctypes.addressof(ds), ctypes.addressof(d), ctypes.sizeof(d))
-        ds.param, ds.grad = ops.addr(self.P32, lo), ops.addr(self.G32, lo)
-        ds.exp_avg, ds.exp_avg_sq = ops.addr(self.M, lo), ops.addr(self.V, lo)
-        ds.max_exp_avg_sq, ds.param16 = ops.addr(self.VMAX, lo), ops.addr(self.P16, lo)
-        ds.n = hi - lo
-        for i in range(d.ngroups):
-            ds.group_end[i] = d.group_end[i] - lo
-        return ops.Call("vqa_adamw_amsgrad", ctypes.byref(ds), desc=ds,
-                        keep=(self.P32, self.G32, self.M, self.V, self.VMAX, self.P16, self.opt_state))
+    def _adam_groups(self):
+        ends, lrs = self.lay.group_of_element()
+        return ends, [self.group_lr.get(g, lr) for g, lr in zip(self.lay.groups, lrs)]
 
     def flush_optimizer(self):
         """Apply a deferred AdamW update now (before reading the parameters outside a step)."""
         if self.defer_opt:
             self._run([c for _, c in self.adam_segs] + [self.clear_pending])
-
-    def set_training(self, mode=True):
-        """model.train() / model.eval(): the dropout kernels read this device flag at run
-        time, so captured graphs stay valid."""
-        self.RNG[2].fill_(1 if mode else 0)
-
-    def configure_optimizer(self, group_lr=None, warmup=None, total=None, max_norm=None, weight_decay=None,
-                            betas=None, eps=None):
-        """Re-plan the clip + AdamW + schedule tail (faster_rcnn_vqa_trainer.py:231-287 knobs)."""
-        if group_lr:
-            self.group_lr.update(group_lr)
-        if warmup is not None:
-            self.warmup = int(warmup)
-        if total is not None:
-            self.total = int(total)
-        if max_norm is not None:
-            self.max_norm = float(max_norm)
-        if weight_decay is not None:
-            self.wd = float(weight_decay)
-        if betas is not None:
-            self.betas = tuple(betas)
-        if eps is not None:
-            self.eps = float(eps)
-        self.opt_calls = []
-        self._plan_optimizer()
-        self.graph = None
 
     def set_grad_scale(self, s):
         """DP: grads are summed over ranks; the average enters as a scale."""
@@ -1374,11 +1027,6 @@ class VQAEngine:
         self.graph = None
 
     # ------------------------------------------------------------------ execution
-    def _run(self, calls):
-        s = L.stream_handle()
-        for c in calls:
-            c(s)
-
     def load_batch(self, batch, next_images=None):
         """Copy a batch dict (numpy or torch, host or device) into the static input buffers.
         Pipelined engines take the batch's text and targets, and `next_images` = the image
@@ -1439,15 +1087,8 @@ class VQAEngine:
         self.graph = None
 
     def forward(self):
-        if self.defer_opt:                              # the previous step's update, then the forward
-            self._run([c for _, c in self.adam_segs] + [self.clear_pending])
-        self._run(self.fwd_calls)
-
-    def backward(self):
-        self._run(self.bwd_calls)
-
-    def optimizer_step(self):
-        self._run(self.opt_calls)
+        self.flush_optimizer()                          # the previous step's deferred update, then the forward
+        super().forward()
 
     def _run_step_streams(self, optimizer=True):
         """One step with graph-level concurrency: the frozen-ResNet + ConvTranspose2d
@@ -1468,12 +1109,10 @@ class VQAEngine:
         f = self.fwd_calls
         p0, p1, p2 = self._fsplit
         self._run(f[:p0])                                  # rng advance
-        fork = torch.cuda.Event()
-        fork.record(main)
-        side.wait_event(fork)
+        _after(side, main)
         vis, txt = f[p0:p1], f[p1:p2]
         if self.defer_opt:
-            self._forward_branches_deferred(fork, main, side, vis, txt)
+            self._forward_branches_deferred(main, side, vis, txt)
         else:
             self._forward_branches(main, side, vis, txt)
         self._run(f[p2:])                                  # SGA + head
@@ -1495,9 +1134,7 @@ class VQAEngine:
                 j += 1
         for c in txt[j:]:
             c(hs)
-        join = torch.cuda.Event()
-        join.record(side)
-        main.wait_event(join)
+        _after(main, side)
 
     def _t5_waits(self, i):
         """The deferred AdamW ranges T5 layer i's calls must find applied, beyond those of the
@@ -1509,7 +1146,7 @@ class VQAEngine:
             w.append(f"t5.{i + 1}")
         return w
 
-    def _forward_branches_deferred(self, fork, main, side, vis, txt):
+    def _forward_branches_deferred(self, main, side, vis, txt):
         """The two forward branches with the previous step's AdamW ranges on a third stream.
         Capture order is submission order for a replayed graph, so the ranges are issued
         two T5 layers ahead of the layer calls that wait for them (issuing all of them
@@ -1543,9 +1180,9 @@ class VQAEngine:
         vpost = vis[self._fvis_param - p0:]                # ConvTranspose2d + SGA block 0 k/v
         bounds = starts + [len(txt)]
         j = 0
-        feed = getattr(self, "_res_feed", None)            # the next batch's ResNet (res_order interleave)
+        feed = self._res_feed                              # the next batch's ResNet (res_order interleave)
         nres = len(feed[0]) if feed else 0
-        head = min(nres, getattr(self, "res_head", 4))
+        head = min(nres, self.res_head)
 
         def res_upto(n):
             while feed and feed[0] and nres - len(feed[0]) < n:
@@ -1572,9 +1209,7 @@ class VQAEngine:
                 for c in vpost:
                     c(hm)
                 vpost = []
-        join = torch.cuda.Event()
-        join.record(side)
-        main.wait_event(join)
+        _after(main, side)
         main.wait_event(ev[f"t5.{nl - 1}"])               # the last range issued (stream order)
         self.clear_pending(hm)                             # the update is applied: once only
         assert set(ev) == set(order)
@@ -1590,9 +1225,7 @@ class VQAEngine:
         b = self.bwd_calls
         q0, q1 = self._bsplit
         self._run_tagged(b[:q0], main, wside)              # head + SGA backward
-        fork2 = torch.cuda.Event()
-        fork2.record(main)
-        side.wait_event(fork2)
+        _after(side, main)
         with torch.cuda.stream(side):
             self._run(b[q0:q1])                            # scaler dW / db
             if sq_overlap:                                 # a full step: the untouched embedding rows'
@@ -1602,9 +1235,7 @@ class VQAEngine:
 
             def to_side(calls):                            # after everything issued so far on main / wside
                 for st in ((main, wside) if self.dw_stream else (main,)):
-                    ev = torch.cuda.Event()
-                    ev.record(st)
-                    side.wait_event(ev)
+                    _after(side, st)
                 with torch.cuda.stream(side):
                     self._run(calls)
             m1 = self._sq_split[0] if self._sq_split is not None else None
@@ -1620,9 +1251,7 @@ class VQAEngine:
         else:
             self._run_tagged(b[q1:], main, wside)          # T5 backward + embedding
         for st in (side, wside):
-            join2 = torch.cuda.Event()
-            join2.record(st)
-            main.wait_event(join2)
+            _after(main, st)
 
     def _run_tagged(self, calls, main, wside):
         """Run `calls` in order on `main`, except runs of side-tagged calls (weight
@@ -1642,9 +1271,7 @@ class VQAEngine:
             while j < n and calls[j].side == calls[i].side:
                 j += 1
             if calls[i].side:
-                ev = torch.cuda.Event()
-                ev.record(main)
-                wside.wait_event(ev)
+                _after(wside, main)
                 with torch.cuda.stream(wside):
                     self._run(calls[i:j])
             else:
@@ -1675,7 +1302,7 @@ class VQAEngine:
         into the captured step (re-capture needed: the graph is dropped).  destroy=False keeps the
         masked stream alive and returns it (tools/queue_probe.py times the step while it exists);
         the caller then owns the handle (hipStreamDestroy)."""
-        h = getattr(self, "_rstream_handle", None)
+        h = self._rstream_handle
         if h is None:
             return None
         torch.cuda.synchronize(self.dev)
@@ -1695,16 +1322,12 @@ class VQAEngine:
     def _res_external_step(self):
         main = torch.cuda.current_stream(self.dev)
         self.copy_f4(L.stream_handle(main))
-        fork = torch.cuda.Event()
-        fork.record(main)
+        _after(self._rstream, main)                        # the ResNet waits for the copy, not for the chain
         for g in self.graph:
             g.replay()
-        self._rstream.wait_event(fork)
         with torch.cuda.stream(self._rstream):
             self._run(self.res_calls)
-        join = torch.cuda.Event()
-        join.record(self._rstream)
-        main.wait_event(join)
+        _after(main, self._rstream)
 
     def _step_pipelined(self):
         """One pipelined step: F4 <- F4N (features of this batch, made last step), then the
@@ -1717,17 +1340,15 @@ class VQAEngine:
             self.run_backward_streams(sq_overlap=True)
             self._run(self.tail_calls)
             return
-        if not (torch.cuda.is_current_stream_capturing() and getattr(self, "res_order", "first") == "root"):
+        if not (torch.cuda.is_current_stream_capturing() and self.res_order == "root"):
             self.copy_f4(L.stream_handle(main))            # ("root": issued before the replay, train_step)
-        fork = torch.cuda.Event()
-        fork.record(main)
-        self._rstream.wait_event(fork)
+        _after(self._rstream, main)
 
         # the ResNet branch is captured first: a replayed graph submits nodes in capture order,
         # and issuing it after T5 layer 0 / 1 / 3 measured 0.7 ms slower
         # (res_order "last": the same dependencies, the ResNet's nodes created after the chain's)
-        last = getattr(self, "res_order", "first") == "last"
-        inter = getattr(self, "res_order", "first") == "interleave"
+        last = self.res_order == "last"
+        inter = self.res_order == "interleave"
         if inter:                    # issued between the T5 encoder layers (_forward_branches_deferred)
             self._res_feed = [list(self.res_calls), L.stream_handle(self._rstream)]
         elif not last:
@@ -1742,16 +1363,14 @@ class VQAEngine:
         if last:
             with torch.cuda.stream(self._rstream):
                 self._run(self.res_calls)
-        join = torch.cuda.Event()
-        join.record(self._rstream)
-        main.wait_event(join)
+        _after(main, self._rstream)
 
     def train_step(self):
         """zero_grad -> forward -> backward -> (all-reduce) -> clip -> AdamW -> sched, all on-device."""
         if self.graph is not None and self.res_external:
             self._res_external_step()
             return
-        if self.graph is not None and self.pipeline and getattr(self, "res_order", "first") == "root":
+        if self.graph is not None and self.pipeline and self.res_order == "root":
             self.copy_f4(L.stream_handle(torch.cuda.current_stream(self.dev)))
         if self.graph is not None:
             for g in self.graph:
@@ -1796,7 +1415,7 @@ class VQAEngine:
         self.graph = parts
 
     def _new_graph(self):
-        return torch.cuda.CUDAGraph(keep_graph=getattr(self, "_keep_graph", False))
+        return torch.cuda.CUDAGraph(keep_graph=self._keep_graph)
 
     def _capture_parts(self, s):
         if self.allreduce is None:
@@ -1885,9 +1504,7 @@ class VQAEngine:
         side = self._side
         f = self.fwd_calls
         p0, p1, p2 = self._fsplit
-        fork = torch.cuda.Event()
-        fork.record(main)
-        side.wait_event(fork)
+        _after(side, main)
         self._forward_branches(main, side, f[p0:p1], f[p1:p2])
         self._run(f[p2:])
         self.eval_call(L.stream_handle(main))
@@ -1915,7 +1532,7 @@ class VQAEngine:
                 self._run_eval_streams()
         for dst, src in zip((self.opt_state, self.RNG, self.EVAL_BUF), saved):
             dst.copy_(src)
-        if getattr(self, "_keep_graph", False):
+        if self._keep_graph:
             g.instantiate()
         self.eval_graph = g
 
@@ -1952,156 +1569,12 @@ class VQAEngine:
         out["targets"] = h[16 + cap:16 + cap + n].tolist()
         return out
 
-    # ------------------------------------------------------------------ GEMM autotuning
-    def _tune_scratch(self, d):
-        """Zero-filled split-K workspace shared by every candidate timed during tuning
-        (one stream, one launch at a time; each launch leaves its counters zero)."""
-        need = int(L.load().vqa_gemm_workspace_bytes(ctypes.byref(d)))
-        if self._scratch is None or self._scratch.numel() * 4 < need:
-            self._scratch = torch.zeros(need // 4 + 4, dtype=torch.int32, device=self.dev)
-        return self._scratch
-
-    def _apply_choice(self, c, choice):
-        """Tuning-table value = tile config + 100 * splitk (splitk 0/1 = no split).  A split
-        call gets its own zero-filled workspace, kept alive by the call."""
-        d = c.desc
-        d.config, sk = choice % 100, choice // 100
-        if d.norm:                                         # a norm tail: no split-K, its workspace stays
-            assert sk <= 1 and d.config in L.GEMM_NORM, choice
-            return
-        if sk > 1:
-            ops.set_splitk(d, sk)
-            ws = ops.splitk_workspace(d, self.dev)
-            ops.set_splitk(d, sk, ws)
-            c.keep = tuple(c.keep or ()) + (ws,)
-        else:
-            ops.set_splitk(d, 0)
-
-    def autotune(self, reps=5, table=None, save=None, cold=False):
-        """Pick the fastest (tile config, split-K) for every prepared GEMM by timing
-        them in place (HIP events).  Tile configs differ only in speed: each output
-        element is accumulated in the same K order whatever the tile.  Split-K
-        (tried only for grids < 512 tiles) re-associates the K sum in a fixed slice
-        order, so a given choice is deterministic; DP ranks stay in lockstep either
-        way because they apply the same all-reduced gradient.  The committed table
-        (`table`) pins the choices of known shapes.  Run after a batch is loaded and
-        one forward/backward has filled the activations; it scribbles only on
-        buffers the next step recomputes.
-
-        cold: time every candidate from cold caches (a 512 MiB write evicts L2 and the
-        Infinity Cache before each timed launch), as the launches run inside the step,
-        where operands were written by another kernel or last read a step ago; warm
-        back-to-back replays favour shallow rings.  Uses (and fills) its own cache."""
-        import json
-        import os
-        cache = _TUNE_CACHE_COLD if cold else _TUNE_CACHE
-        if table and os.path.exists(table):                # measured table (tools: bench --tune-save)
-            for k, v in json.load(open(table)).items():
-                cache.setdefault(k, int(v))
-        s = L.stream_handle()
-        lib = L.load()
-        st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        flush = torch.empty(128 << 20, dtype=torch.float32, device=self.dev) if cold else None
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
-
-        def time_call(c):
-            c(s)
-            if not cold:
-                st.record()
-                for _ in range(reps):
-                    c(s)
-                en.record()
-                en.synchronize()
-                return st.elapsed_time(en)
-            for a, b in evs:
-                flush.fill_(1.0)
-                a.record()
-                c(s)
-                b.record()
-            evs[-1][1].synchronize()
-            return sorted(a.elapsed_time(b) for a, b in evs)[reps // 2]
-        chosen = {}
-        timed = []                                         # shapes not in the table: timed here
-        extra = self.res_calls if self.pipeline else []
-        for c in extra + self.fwd_calls + self.bwd_calls:
-            if c.name == "vqa_gemm_pair":
-                d1, d2 = c.desc
-                key = repr(("pair", _gemm_key(d1), _gemm_key(d2)))
-                if key not in cache:
-                    timed.append(key)
-                    best = None
-                    for c1 in (3, 4, 6, 7):
-                        for c2 in (3, 4, 6, 7):
-                            d1.config, d2.config = c1, c2
-                            t = time_call(c)
-                            if best is None or t < best[0]:
-                                best = (t, c1 * 10 + c2)
-                    cache[key] = best[1]
-                d1.config, d2.config = cache[key] // 10, cache[key] % 10
-                chosen[key] = cache[key]
-                continue
-            if c.name != "vqa_gemm" or c.desc.relu >= 2:        # GELU / tanh: one fixed kernel
-                continue
-            d = c.desc
-            key = repr(_gemm_key(d))
-            if key not in cache:
-                timed.append(key)
-                best = None
-                nk = -(-d.k // 64)
-                for cfg in range(1, lib_gemm_configs() + 1):
-                    if (cfg in L.GEMM_KC_B_ONLY and d.b_trans) or ((cfg in L.GEMM_PATCH_ONLY) != (d.a_conv == 2)):
-                        continue
-                    if d.fp8 and cfg not in L.GEMM_FP8:
-                        continue
-                    if d.norm and cfg not in L.GEMM_NORM:
-                        continue                           # tile configs with a row-norm tail
-                    bm, bn, _ = L.GEMM_TILES[cfg]
-                    tiles = -(-d.m // bm) * -(-d.n // bn) * max(1, d.batch)
-                    if cfg in L.GEMM_BK128 and (d.a_conv or d.b_conv):
-                        continue                           # 128-deep k-tiles: plain operands only
-                    if cfg in L.GEMM_K64_ONLY and (d.k > 64 or d.a_conv or d.b_conv):
-                        continue                           # one k-tile, plain operands only
-                    if d.norm:                             # no split-K; the descriptor's workspace = its counters
-                        d.config = cfg
-                        t = time_call(c)
-                        if best is None or t < best[0]:
-                            best = (t, cfg)
-                        continue
-                    for sk in SPLITS:
-                        # split only grids that leave CUs idle, with >= 2 k-tiles per slice
-                        if sk > 1 and (tiles >= 512 or nk < 2 * sk or tiles > 16384 or d.a_conv == 2
-                                       or cfg in L.GEMM_BK128 or cfg in L.GEMM_K64_ONLY):
-                            continue
-                        d.config = cfg
-                        ops.set_splitk(d, sk)
-                        ops.set_splitk(d, sk, self._tune_scratch(d) if sk > 1 else None)
-                        t = time_call(c)
-                        if best is None or t < best[0]:
-                            best = (t, cfg + 100 * sk)
-                if not d.norm:
-                    ops.set_splitk(d, 0)
-                cache[key] = best[1]
-            self._apply_choice(c, cache[key])
-            chosen[key] = cache[key]
-        torch.cuda.synchronize(self.dev)
-        if timed:
-            import sys
-            print(f"autotune: {len(timed)} GEMM shapes not in the table, timed at start-up "
-                  f"(their choice, and with split-K the rounding, can vary by box): {timed}", file=sys.stderr)
-        self._scratch = None
-        self.graph = None
-        self.eval_graph = None                             # it holds the forward GEMMs' old tile choices
-        if save:
-            json.dump(dict(sorted(chosen.items())), open(save, "w"), indent=0)
-        return chosen
-
     # ------------------------------------------------------------------ readouts (tests / API)
-    def forward_backward(self, batch):
-        self.load_batch(batch)
-        self.forward()
-        self.backward()
-        torch.cuda.synchronize(self.dev)
-        return self.LOGP[:self.rows].cpu().numpy(), float(self.LOSS.item())
+    def _model_specs(self):
+        return S.model_specs(self.vision, self.A, self.NB, self.dims)
+
+    def _tune_calls(self):
+        return (self.res_calls if self.pipeline else []) + super()._tune_calls()
 
     def log_probs(self):
         return self.LOGP[:self.rows]
@@ -2109,82 +1582,12 @@ class VQAEngine:
     def loss(self):
         return self.LOSS
 
-    def grad_norm(self):
-        return float(self.G32.double().norm()) * self.grad_scale
-
-    def group_grad_norms(self):
-        out = {}
-        for g, (a, e) in self.lay.groups.items():
-            out[g] = float(self.G32[a:e].double().norm()) * self.grad_scale
-        return out
-
-    def last_grad_norm(self):
-        return float(self.opt_state[L.ST_GRAD_NORM].item())
-
-    def state_dict(self):
-        """Reference-layout state_dict (SURVEY Appendix B keys), fp32 numpy."""
-        self.flush_optimizer()
-        sd = dict(self._frozen)
-        sd.update(self.lay.unpack(self.P32.cpu().numpy()))
-        specs = S.model_specs(self.vision, self.A, self.NB, self.dims)
-        return {k: sd[k] for k in specs}
-
-    def optimizer_state(self):
-        """AdamW(amsgrad) state in reference layout: ({key: exp_avg}, {key: exp_avg_sq},
-        {key: max_exp_avg_sq}, step, dropout RNG {seed, counter, training}).  The pending
-        deferred update is applied first, as state_dict() does."""
-        self.flush_optimizer()
-        torch.cuda.synchronize(self.dev)
-        unpack = lambda t: self.lay.unpack(t.cpu().numpy())
-        return (unpack(self.M), unpack(self.V), unpack(self.VMAX), float(self.opt_state[L.ST_STEP].item()),
-                self.RNG.cpu().numpy().copy())
-
-    def load_optimizer_state(self, exp_avg, exp_avg_sq, max_exp_avg_sq, step, rng=None):
-        """Restore what optimizer_state() returned (keys missing from the dicts: zero state)."""
-        self.flush_optimizer()
-        zeros = {k: np.zeros(sg, np.float32) for k, sg in S.model_specs(self.vision, self.A, self.NB, self.dims).items()
-                 if k in set(self.lay.trainable_keys)}
-        for arena, st in ((self.M, exp_avg), (self.V, exp_avg_sq), (self.VMAX, max_exp_avg_sq)):
-            full = dict(zeros)
-            full.update({k: np.asarray(v, np.float32) for k, v in st.items() if k in full})
-            arena.copy_(torch.from_numpy(self.lay.pack(full)))
-        self.opt_state.zero_()
-        self.opt_state[L.ST_STEP] = float(step)
-        if rng is not None:
-            self.RNG.copy_(torch.as_tensor(np.asarray(rng).astype(np.uint32).view(np.int32)))
-        torch.cuda.synchronize(self.dev)
-
     def segment_grad(self, name):
         return self.g32[name]
 
-    def param_view(self, key):
-        """(parameter, gradient) device views of reference state-dict entry `key` inside the
-        flat fp32 arenas (no copy: they alias the engine's live weights / gradients).  The
-        q|k|v and k|v stacks are row blocks, so their parts are exact reference-shaped views;
-        the ConvTranspose2d scaler is stored as the flipped conv weight, so its view has the
-        kernel layout [768, 3, 3, Cin] (layout.py).  None if `key` is not trainable here."""
-        specs = S.model_specs(self.vision, self.A, self.NB, self.dims)
-        for sg in self.lay.segments.values():
-            if key not in sg.parts:
-                continue
-            p32, g32 = self.p32[sg.name], self.g32[sg.name]
-            if sg.kind == "convT":
-                return p32, g32
-            if sg.kind == "flat":
-                return p32.view(specs[key]), g32.view(specs[key])
-            row = 0
-            for part in sg.parts:
-                n = specs[part][0]
-                if part == key:
-                    return p32[row:row + n].view(specs[key]), g32[row:row + n].view(specs[key])
-                row += n
-        return None
-
     def refresh_shadow(self):
-        """Re-derive the bf16 GEMM shadow from the fp32 masters (after writing weights through
-        param_view / ParameterGroup views)."""
-        self.P16.copy_(self.P32)
-        self._run(self.quant_all)
+        super().refresh_shadow()
+        self._run(self.quant_all)                       # ... and the e4m3 weight copies (fp8)
 
     def layer4_features(self):
         """The frozen ResNet's layer4 map of the current batch as NCHW fp32 (the kernels keep

@@ -1,0 +1,491 @@
+"""EngineBase: what the two training engines (engine.VQAEngine, vit_engine.VitVQAEngine)
+share -- the flat fp32 parameter / gradient / AdamW arenas with their bf16 shadow, the
+builders of prepared library calls (every tensor a call bakes an address of is recorded in
+its `keep`), the AdamW descriptors (the full arena and any sub-range of it), the eager
+forward / backward / optimizer entry points, and the readouts in reference layout
+(state_dict, optimizer state, parameter views).  An engine adds its own plan:
+`_plan_forward` / `_plan_backward` / `_plan_optimizer`, `load_batch`, `train_step`, `capture`.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes
+import gc
+
+import numpy as np
+import torch
+
+from . import lib as L
+from . import ops
+from . import tune
+
+BF16, F32, I64 = torch.bfloat16, torch.float32, torch.int64
+
+# dropout site ids (the hash key of each nn.Dropout application of the step)
+SITE_EMBED, SITE_FINAL = 1, 2                  # T5Stack: dropout(inputs_embeds) :725, dropout(final_ln) :745
+
+
+def t5_site(layer, kind):
+    """kind 0 attention probs (:168), 1 attention residual branch (:400), 2 FF inner (:86), 3 FF residual (:140)"""
+    return 16 + 4 * layer + kind
+
+
+class _Seq:
+    """Several prepared calls issued as one (a deferred AdamW range and the e4m3 weight
+    copies that follow it)."""
+    def __init__(self, calls):
+        self.calls = calls
+
+    def __call__(self, stream):
+        for c in self.calls:
+            c(stream)
+
+
+@contextlib.contextmanager
+def no_gc_capture():
+    """Stream capture with the cyclic garbage collector held off.  Engines (and the graphs /
+    tensors they own) are reclaimed through reference cycles; a collection that lands inside
+    a capture destroys another engine's graph execs and frees its blocks while the capture
+    is being recorded (measured: the later replay of the captured graph crashed in the
+    runtime).  Collect first, then keep the collector off until the capture has ended."""
+    was = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
+
+
+def _after(stream, other):
+    """`stream` waits for everything issued so far on `other` (an event, no host sync)."""
+    if stream is other:
+        return
+    ev = torch.cuda.Event()
+    ev.record(other)
+    stream.wait_event(ev)
+
+
+_WARNED_ATTN = set()
+
+
+def _check_attn_path(d, fn):
+    """Say it loudly (once per shape) when a planned attention call would run the scalar VALU
+    kernel (include/vqa_hip.h vqa_attn_path): it is correct but an order of magnitude slower
+    than the MFMA kernels, which cover lq <= 32, lk <= 160 (key mask: lk <= 64)."""
+    path = L.load().vqa_attn_path(ctypes.byref(d), int(fn == "vqa_attn_bwd"))
+    if path == L.ATTN_VALU:
+        key = (fn, d.lq, d.lk, d.dh, bool(d.key_mask))
+        if key not in _WARNED_ATTN:
+            _WARNED_ATTN.add(key)
+            import warnings
+            warnings.warn(f"{fn}: lq={d.lq} lk={d.lk} dh={d.dh} key_mask={bool(d.key_mask)} runs the scalar VALU "
+                          "attention kernel (no MFMA kernel covers this shape)", RuntimeWarning, stacklevel=3)
+    return path
+
+
+def _h2d(dst, src):
+    """dst <- src (numpy / torch, host or device).  Asynchronous only from device or pinned
+    memory: an async copy out of a pageable temporary (freed when this returns) may be read
+    by the runtime after the free."""
+    src = torch.as_tensor(src).to(dst.dtype).reshape(dst.shape)
+    dst.copy_(src, non_blocking=src.is_cuda or src.is_pinned())
+
+
+IGNORE_INDEX = -100          # nn.NLLLoss's default ignore_index: the head skips rows with a target < 0
+
+
+def batch_rows(batch, key, planned, allow_empty=False):
+    """Rows of a collate batch (the reference's loaders have no drop_last, so an epoch's last
+    batch is short: faster_rcnn_vqa_trainer.py:172-197); 1 <= rows <= the planned batch (0 rows
+    only for a data-parallel rank whose share of the global batch is empty: allow_empty)."""
+    n = int(torch.as_tensor(batch[key]).shape[0])
+    if not (0 if allow_empty else 1) <= n <= planned:
+        lo = 0 if allow_empty else 1
+        raise ValueError(f"{key}: batch of {n} rows; this engine is planned for {lo}..{planned} rows")
+    return n
+
+
+def load_rows(dst, src, n, fill=None, empty_fill=0):
+    """dst[:n] <- src (n rows); the planned rows past n are padding: copies of rows 0..n-1
+    (real samples, so every activation stays finite) or `fill` (targets: IGNORE_INDEX, so the
+    padded rows add nothing to the loss or to any gradient -- the NLL mean runs over the n
+    real rows).  n = 0 (an empty data-parallel rank): every row is `fill`, else `empty_fill`
+    (finite inputs whose targets are all ignored: the rank's gradient is exactly zero)."""
+    if src is None:
+        return
+    B = dst.shape[0]
+    if n == 0:
+        dst.fill_(fill if fill is not None else empty_fill)
+        return
+    _h2d(dst[:n] if n < B else dst, src)
+    if n == B:
+        return
+    if fill is not None:
+        dst[n:].fill_(fill)
+        return
+    i = n
+    while i < B:                                   # doubling copies of the real rows
+        k = min(i, B - i)
+        dst[i:i + k].copy_(dst[:k])
+        i += k
+
+
+class EngineBase:
+    TIED = {}                         # reference keys that alias another trainable key (tied weights)
+
+    def __init__(self, device, dropout, seed, warmup, total, max_norm, betas, eps, weight_decay, grad_scale=1.0,
+                 group_lr=None):
+        L.load()
+        self.dev = torch.device(device)
+        self.p_drop, self.seed = float(dropout), int(seed)
+        self.warmup, self.total, self.max_norm = warmup, total, max_norm
+        self.betas, self.eps, self.wd = betas, eps, weight_decay
+        self.grad_scale = grad_scale
+        self.group_lr = dict(group_lr or {})  # per-group LR overrides (trainer optimizer_kwargs)
+        self.fp8 = False                  # e4m3 forward weight GEMMs (VQAEngine, config 5)
+        self.graph = None
+        self.eval_graph = None            # a forward-only evaluation graph (VQAEngine.eval_capture)
+        self._scratch = None              # split-K workspace used while autotuning
+        self._jobs = []                   # column-sum reductions queued by _defer until _flush
+
+    # ------------------------------------------------------------------ hooks
+    def _model_specs(self):
+        """{reference state-dict key: shape} of the whole model."""
+        raise NotImplementedError
+
+    def _trainable_keys(self):
+        """The reference keys held in the flat arenas (tied aliases not among them)."""
+        return [k for s in self.lay.segments.values() for k in s.parts]
+
+    def _adam_groups(self):
+        """(ends, lrs): the end offset and learning rate of each parameter group of the layout."""
+        raise NotImplementedError
+
+    def _tune_calls(self):
+        """The prepared calls whose GEMMs autotune() times."""
+        return self.fwd_calls + self.bwd_calls
+
+    def _alloc_shadow_arenas(self):
+        """Parameter shadows beyond the bf16 one, allocated between G32 and the AdamW moments."""
+
+    def flush_optimizer(self):
+        """Apply a deferred AdamW update now (nothing is deferred unless an engine says so)."""
+
+    # ------------------------------------------------------------------ allocation
+    def _t(self, shape, dtype=F32, zero=False):
+        f = torch.zeros if zero else torch.empty
+        return f(shape, dtype=dtype, device=self.dev)
+
+    def _alloc_arenas(self, sd):
+        lay = self.lay
+        self.P32 = torch.from_numpy(lay.pack(sd)).to(self.dev)
+        self.P16 = self.P32.to(BF16)
+        self.G32 = self._t(lay.total, zero=True)
+        self._alloc_shadow_arenas()
+        self.M, self.V, self.VMAX = (self._t(lay.total, zero=True) for _ in range(3))
+        self.p32, self.p16, self.g32 = {}, {}, {}
+        for s in lay.segments.values():
+            sl = slice(s.offset, s.offset + s.numel)
+            self.p32[s.name] = self.P32[sl].view(s.shape)
+            self.p16[s.name] = self.P16[sl].view(s.shape)
+            self.g32[s.name] = self.G32[sl].view(s.shape)
+        self.opt_state = self._t(L.ST_FLOATS, zero=True)
+        # dropout RNG state {seed, counter, training}; the forward's first call advances the counter
+        self.RNG = torch.from_numpy(np.array([self.seed & 0xFFFFFFFF, 0, 1, 0], np.uint32).view(np.int32)).to(self.dev)
+
+    # ------------------------------------------------------------------ call helpers
+    # Every helper records the tensors it bakes into a call (ops.Call.keep), so no
+    # buffer can be freed while a prepared call still points at it.  Raw int
+    # addresses (sub-views made with ops.addr) must come from tensors that are
+    # passed too or are engine attributes.
+    def _gemm(self, lst, a, b, m, n, k, keep=(), **kw):
+        ts = [a, b] + [v for v in kw.values() if isinstance(v, torch.Tensor)] + list(keep)
+        lst.append(ops.gemm_call(ops.gemm_desc(a, b, m, n, k, **kw), [t for t in ts if isinstance(t, torch.Tensor)]))
+
+    def _call(self, lst, name, *args, extra=()):
+        ts = tuple(a for a in args if isinstance(a, torch.Tensor)) + tuple(extra)
+        lst.append(ops.Call(name, *[ops.addr(a) if isinstance(a, torch.Tensor) else a for a in args], keep=ts))
+
+    def _attn(self, lst, fn, drop=None, keep=(), **kw):
+        d = L.AttnDesc()
+        for k, v in kw.items():
+            setattr(d, k, ops.addr(v) if isinstance(v, torch.Tensor) else v)
+        ts = tuple(v for v in kw.values() if isinstance(v, torch.Tensor)) + tuple(keep)
+        dd = self._drop(drop) if drop is not None else None
+        if dd is not None:
+            d.drop = dd
+            ts = ts + (self.RNG,)
+        _check_attn_path(d, fn)
+        lst.append(ops.Call(fn, ctypes.byref(d), keep=ts, desc=d))
+
+    def _drop(self, site):
+        """vqa_dropout for `site` (None when dropout is off)."""
+        if self.p_drop <= 0.0:
+            return None
+        return L.Dropout(self.p_drop, site, self.RNG.data_ptr())
+
+    def _dptr(self, site, keep):
+        """`const vqa_dropout*` argument (0 = none); the struct is kept alive through `keep`."""
+        d = self._drop(site)
+        if d is None:
+            return None
+        keep.append(d)
+        return ctypes.addressof(d)
+
+    def _set_drop(self, call, site):
+        """Dropout `site` (None: none) on the output of a prepared GEMM."""
+        d = self._drop(site) if site is not None else None
+        if d is not None:
+            call.desc.drop = d
+            call.keep = call.keep + (self.RNG,)
+
+    @property
+    def drop_scale(self):
+        """1/(1-p) in fp32, the multiplier of a kept element (as the kernels compute it)."""
+        p = np.float32(self.p_drop)
+        return float(np.float32(1.0) / (np.float32(1.0) - p))
+
+    def _linear(self, lst, x16, wname, m, out32=None, out16=None, bias=True, relu=False, res32=None, drop=None,
+                norm=None):
+        """norm: vqa_gemm_desc norm fields (ops.gemm_desc keywords) of a row norm fused behind
+        this GEMM (fuse_norm), or None."""
+        nkw = dict(norm or {})
+        nkeep = tuple(nkw.pop("keep", ()))
+        if self.fp8 and self._is_fp8(wname):               # e4m3 operands (VQAEngine's fp8 arenas)
+            x8, xs = self._quant_act(lst, (wname, "x"), x16, m)
+            w8, ws = self._w8(wname)
+            n, k = w8.shape
+            self._gemm(lst, x8, w8, m, n, k, lda=k, ldb=k, c32=out32, ldc32=n, c16=out16, ldc16=n,
+                       bias=self.p32[wname[:-1] + "b"] if bias else None, relu=relu, res32=res32, ldres=n, fp8=True,
+                       scale_a=xs, scale_b=ws, keep=(self.W8, self.WSC) + nkeep, **nkw)
+        else:
+            w = self.p16[wname]
+            n, k = w.shape
+            self._gemm(lst, x16, w, m, n, k, lda=k, ldb=k, c32=out32, ldc32=n, c16=out16, ldc16=n,
+                       bias=self.p32[wname[:-1] + "b"] if bias else None, relu=relu, res32=res32, ldres=n, keep=nkeep,
+                       **nkw)
+        self._set_drop(lst[-1], drop)
+
+    def _dx(self, lst, dy16, wname, m, out32=None, out16=None, res32=None, mask16=None, beta=0.0, alpha=1.0):
+        """dX[m, k] = alpha * dY[m, n] W[n, k]  (+res) (*mask>0) (+beta*out32)"""
+        w = self.p16[wname]
+        n, k = w.shape
+        self._gemm(lst, dy16, w, m, k, n, lda=n, ldb=k, b_trans=True, c32=out32, ldc32=k, c16=out16, ldc16=k,
+                   res32=res32, ldres=k, mask16=mask16, ldmask=k, beta=beta, alpha=alpha)
+
+    def _dw(self, lst, dy16, x16, wname, rows, bias_from=None):
+        """dW[n, k] = dY[rows, n]^T X[rows, k]; optional bias grad = colsum(bias_from), bf16.
+        Tagged `side`: nothing on the dX chain reads them, so a step with a weight-gradient
+        stream (VQAEngine._run_tagged) runs them beside the chain, joined before the optimizer."""
+        g = self.g32[wname]
+        n, k = g.shape
+        self._gemm(lst, dy16, x16, n, k, rows, lda=n, ldb=k, a_trans=True, b_trans=True, c32=g, ldc32=k)
+        lst[-1].side = True
+        if bias_from is not None:
+            assert bias_from.shape[-1] == n
+            self._bias_colsum(lst, bias_from, rows, wname[:-1] + "b")
+
+    def _bias_colsum(self, lst, dy16, rows, bname):
+        """A Linear bias gradient = column sums of its bf16 output gradient: the partial
+        column sums now, the final sum deferred (_flush)."""
+        lib = L.load()
+        n = dy16.shape[-1]
+        ws = self._t(lib.vqa_colsum_workspace_floats(rows, n))
+        self._call(lst, "vqa_colsum", dy16, 1, rows, n, n, None, 0.0, ws)
+        self._defer(ws, lib.vqa_colsum_parts(rows), n, n, self.g32[bname])
+
+    def _defer(self, ws, parts, stride, cols, out, beta=0.0, offset=0):
+        """Queue the final reduction out = beta*out + sum_p ws[offset + p*stride + c] (a norm
+        weight/bias or Linear bias gradient whose per-block partial rows a backward kernel
+        wrote); _flush() finishes every queued one in a single vqa_colsum_batched launch."""
+        self._jobs.append((ops.addr(ws) + 4 * offset, ops.addr(out), stride, parts, cols, beta, (ws, out)))
+
+    def _flush(self, lst):
+        if not self._jobs:
+            return
+        arr = (L.ColsumJob * len(self._jobs))()
+        blk = 0
+        keep = []
+        for j, (ws, out, stride, parts, cols, beta, k) in enumerate(self._jobs):
+            arr[j] = L.ColsumJob(ws, out, stride, parts, cols, beta, blk)
+            blk += -(-cols // 64)
+            keep += list(k)
+        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.dev)
+        lst.append(ops.Call("vqa_colsum_batched", raw.data_ptr(), len(self._jobs), blk, keep=tuple(keep) + (raw,)))
+        self._jobs = []
+
+    def _norm_ws(self, rows=None):
+        """A private partial-row workspace for one deferred norm backward over `rows` (T) rows."""
+        return self._t(L.load().vqa_norm_bwd_workspace_floats(self.T if rows is None else rows, self.D))
+
+    def _run(self, calls):
+        s = L.stream_handle()
+        for c in calls:
+            c(s)
+
+    # ------------------------------------------------------------------ AdamW descriptors
+    def _adam_desc_full(self):
+        """The AdamW-amsgrad descriptor of the whole flat arena."""
+        d = L.AdamWDesc()
+        d.param, d.grad = self.P32.data_ptr(), self.G32.data_ptr()
+        d.exp_avg, d.exp_avg_sq, d.max_exp_avg_sq = self.M.data_ptr(), self.V.data_ptr(), self.VMAX.data_ptr()
+        d.param16 = self.P16.data_ptr()
+        d.n = self.lay.total
+        ends, lrs = self._adam_groups()
+        d.ngroups = len(ends)
+        for i, (e, lr) in enumerate(zip(ends, lrs)):
+            d.group_end[i], d.group_lr[i] = e, lr
+        d.beta1, d.beta2, d.eps, d.weight_decay = self.betas[0], self.betas[1], self.eps, self.wd
+        d.grad_scale = self.grad_scale
+        d.state = self.opt_state.data_ptr()
+        return d
+
+    def _adam_range_desc(self, lo, hi):
+        """self._adam_desc restricted to flat elements [lo, hi): the six arena pointers moved to
+        `lo`, n = hi - lo, the group ends relative to `lo`; every other field as in the full one."""
+        d = self._adam_desc
+        ds = L.AdamWDesc()
+        ctypes.memmove(ctypes.addressof(ds), ctypes.addressof(d), ctypes.sizeof(d))
+        ds.param, ds.grad = ops.addr(self.P32, lo), ops.addr(self.G32, lo)
+        ds.exp_avg, ds.exp_avg_sq = ops.addr(self.M, lo), ops.addr(self.V, lo)
+        ds.max_exp_avg_sq, ds.param16 = ops.addr(self.VMAX, lo), ops.addr(self.P16, lo)
+        ds.n = hi - lo
+        for i in range(d.ngroups):
+            ds.group_end[i] = d.group_end[i] - lo
+        return ds
+
+    def _adam_keep(self):
+        return (self.P32, self.G32, self.M, self.V, self.VMAX, self.P16, self.opt_state)
+
+    def _adam_call(self, d):
+        return ops.Call("vqa_adamw_amsgrad", ctypes.byref(d), desc=d, keep=self._adam_keep())
+
+    def adam_range_call(self, lo, hi):
+        """The fused AdamW-amsgrad pass over flat parameters [lo, hi) only (the step's device
+        state: clip coefficient, schedule, bias corrections; no-op unless an update is pending)."""
+        return self._adam_call(self._adam_range_desc(lo, hi))
+
+    def configure_optimizer(self, group_lr=None, warmup=None, total=None, max_norm=None, weight_decay=None,
+                            betas=None, eps=None):
+        """Re-plan the clip + AdamW + schedule tail (faster_rcnn_vqa_trainer.py:231-287 knobs)."""
+        if group_lr:
+            self.group_lr.update(group_lr)
+        if warmup is not None:
+            self.warmup = int(warmup)
+        if total is not None:
+            self.total = int(total)
+        if max_norm is not None:
+            self.max_norm = float(max_norm)
+        if weight_decay is not None:
+            self.wd = float(weight_decay)
+        if betas is not None:
+            self.betas = tuple(betas)
+        if eps is not None:
+            self.eps = float(eps)
+        self.opt_calls = []
+        self._plan_optimizer()
+        self.graph = None
+
+    # ------------------------------------------------------------------ execution
+    def set_training(self, mode=True):
+        """model.train() / model.eval(): the dropout kernels read this device flag at run
+        time, so captured graphs stay valid."""
+        self.RNG[2].fill_(1 if mode else 0)
+
+    def forward(self):
+        self._run(self.fwd_calls)
+
+    def backward(self):
+        self._run(self.bwd_calls)
+
+    def optimizer_step(self):
+        self._run(self.opt_calls)
+
+    def autotune(self, reps=5, table=None, save=None, cold=False):
+        """Pick the fastest (tile config, split-K) of every prepared GEMM of _tune_calls()
+        (tune.autotune); the captured graphs hold the old choices and are dropped."""
+        chosen = tune.autotune(self, self._tune_calls(), reps=reps, table=table, save=save, cold=cold)
+        self.graph = None
+        self.eval_graph = None
+        return chosen
+
+    # ------------------------------------------------------------------ readouts (tests / API)
+    def forward_backward(self, batch):
+        self.load_batch(batch)
+        self.forward()
+        self.backward()
+        torch.cuda.synchronize(self.dev)
+        return self.LOGP[:self.rows].cpu().numpy(), float(self.LOSS.item())
+
+    def grad_norm(self):
+        return float(self.G32.double().norm()) * self.grad_scale
+
+    def group_grad_norms(self):
+        return {g: float(self.G32[a:e].double().norm()) * self.grad_scale for g, (a, e) in self.lay.groups.items()}
+
+    def last_grad_norm(self):
+        return float(self.opt_state[L.ST_GRAD_NORM].item())
+
+    def state_dict(self):
+        """Reference-layout state_dict (SURVEY Appendix B keys), fp32 numpy."""
+        self.flush_optimizer()
+        sd = dict(self._frozen)
+        sd.update(self.lay.unpack(self.P32.cpu().numpy()))
+        return {k: sd[k] for k in self._model_specs()}
+
+    def optimizer_state(self):
+        """AdamW(amsgrad) state in reference layout: ({key: exp_avg}, {key: exp_avg_sq},
+        {key: max_exp_avg_sq}, step, dropout RNG {seed, counter, training}) over the trainable
+        keys.  The pending deferred update is applied first, as state_dict() does."""
+        self.flush_optimizer()
+        torch.cuda.synchronize(self.dev)
+        unpack = lambda t: {k: v for k, v in self.lay.unpack(t.cpu().numpy()).items() if k not in self.TIED}  # noqa: E731
+        return (unpack(self.M), unpack(self.V), unpack(self.VMAX), float(self.opt_state[L.ST_STEP].item()),
+                self.RNG.cpu().numpy().copy())
+
+    def load_optimizer_state(self, exp_avg, exp_avg_sq, max_exp_avg_sq, step, rng=None):
+        """Restore what optimizer_state() returned (keys missing from the dicts: zero state)."""
+        self.flush_optimizer()
+        specs = self._model_specs()
+        zeros = {k: np.zeros(specs[k], np.float32) for k in self._trainable_keys()}
+        for arena, st in ((self.M, exp_avg), (self.V, exp_avg_sq), (self.VMAX, max_exp_avg_sq)):
+            full = dict(zeros)
+            full.update({k: np.asarray(v, np.float32) for k, v in st.items() if k in full})
+            arena.copy_(torch.from_numpy(self.lay.pack(full)))
+        self.opt_state.zero_()
+        self.opt_state[L.ST_STEP] = float(step)
+        if rng is not None:
+            self.RNG.copy_(torch.as_tensor(np.asarray(rng).astype(np.uint32).view(np.int32)))
+        torch.cuda.synchronize(self.dev)
+
+    def param_view(self, key):
+        """(parameter, gradient) device views of reference state-dict entry `key` inside the
+        flat fp32 arenas (no copy: they alias the engine's live weights / gradients; a tied key
+        aliases the segment of the key it is tied to).  The q|k|v and k|v stacks are row blocks,
+        so their parts are exact reference-shaped views; the ConvTranspose2d scaler is stored as
+        the flipped conv weight, so its view has the kernel layout [768, 3, 3, Cin] (layout.py).
+        None if `key` is frozen or unknown."""
+        specs = self._model_specs()
+        key = self.TIED.get(key, key)
+        for sg in self.lay.segments.values():
+            if key not in sg.parts:
+                continue
+            p32, g32 = self.p32[sg.name], self.g32[sg.name]
+            if sg.kind == "convT":
+                return p32, g32
+            if sg.kind == "flat":
+                return p32.view(specs[key]), g32.view(specs[key])
+            row = 0
+            for part in sg.parts:
+                n = specs[part][0]
+                if part == key:
+                    return p32[row:row + n].view(specs[key]), g32[row:row + n].view(specs[key])
+                row += n
+        return None
+
+    def refresh_shadow(self):
+        """Re-derive the bf16 GEMM shadow from the fp32 masters (after writing weights through
+        param_view / ParameterGroup views)."""
+        self.P16.copy_(self.P32)

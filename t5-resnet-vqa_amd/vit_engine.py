@@ -26,6 +26,11 @@ such (the norm backward runs with dy = 0); the shared embedding table gets the e
 and decoder token rows in one deterministic scatter.
 Dropout: the counter-hash masks of the ResNet path (p = 0.1 at the T5 sites, 0.5 at
 the fusing layer); the oracle (oracle/vit_oracle.py) restates the same sites.
+
+This module holds the config-4 plan only: the frozen-ViT weights, the activations, the
+forward / backward / optimizer schedules, batch loading, the single-stream step and its
+capture.  Arenas, call builders, the AdamW descriptor, the tuner entry and the state-dict /
+optimizer-state readouts are inherited from engine_base.EngineBase.
 """
 from __future__ import annotations
 
@@ -38,8 +43,8 @@ from . import lib as L
 from . import ops
 from . import synthetic as S
 from . import vit_model as VM
-from .engine import (BF16, F32, I64, IGNORE_INDEX, SITE_EMBED, SITE_FINAL, VQAEngine, batch_rows, load_rows,
-                     no_gc_capture, t5_site)
+from .engine_base import (BF16, F32, I64, IGNORE_INDEX, SITE_EMBED, SITE_FINAL, EngineBase, batch_rows, load_rows,
+                          no_gc_capture, t5_site)
 from .layout import t5_bucket_map
 
 D = S.D_MODEL
@@ -52,53 +57,28 @@ def dec_site(layer, kind):
     return 256 + 8 * layer + kind
 
 
-class VitVQAEngine:
-    # the call helpers, tuner and dropout plumbing are the ResNet engine's
-    _t = VQAEngine._t
-    _gemm = VQAEngine._gemm
-    _call = VQAEngine._call
-    _attn = VQAEngine._attn
-    _drop = VQAEngine._drop
-    _dptr = VQAEngine._dptr
-    drop_scale = VQAEngine.drop_scale
-    _linear = VQAEngine._linear
-    _dx = VQAEngine._dx
-    _defer = VQAEngine._defer
-    _flush = VQAEngine._flush
-    _run = VQAEngine._run
-    set_training = VQAEngine.set_training
-    autotune = VQAEngine.autotune
-    _apply_choice = VQAEngine._apply_choice
-    _tune_scratch = VQAEngine._tune_scratch
-    last_grad_norm = VQAEngine.last_grad_norm
+class VitVQAEngine(EngineBase):
+    TIED = {k: "lang_model.shared.weight" for k in VM.TIED}        # the encoder / decoder embed_tokens
 
     def __init__(self, state_dict, batch=64, seq_len=32, dec_len=VM.DEC_LEN, image_size=VM.VIT_IMAGE,
                  device="cuda:0", warmup=10, total=100, answer_spaces=170, max_norm=1.0, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=0.1, dropout=0.1, seed=0, group_lr=None):
-        L.load()
+        super().__init__(device, dropout, seed, warmup, total, max_norm, betas, eps, weight_decay, group_lr=group_lr)
         if not 1 <= answer_spaces <= 1024:
             raise ValueError(f"answer_spaces={answer_spaces}: the fused answer head supports 1..1024 answers")
         if not (1 <= seq_len <= 32 and 1 <= dec_len <= 32):
             raise ValueError("seq_len and dec_len must be in 1..32 (one 32-query MFMA attention tile)")
         if image_size % VM.VIT_PATCH:
             raise ValueError(f"image_size must be a multiple of {VM.VIT_PATCH}")
-        self.dev = torch.device(device)
-        self.B, self.L, self.Ld, self.H = batch, seq_len, dec_len, image_size
+        self.B, self.L, self.Ld, self.H, self.D = batch, seq_len, dec_len, image_size, D
         self.T, self.TD = batch * seq_len, batch * dec_len
         self.rows = batch                 # real rows of the loaded batch (a short last batch is padded)
         self.NV = VM.vit_tokens(image_size)
         self.TV = batch * self.NV
         self.A = answer_spaces
-        self.p_drop, self.seed = float(dropout), int(seed)
-        self.warmup, self.total, self.max_norm = warmup, total, max_norm
-        self.betas, self.eps, self.wd = betas, eps, weight_decay
-        self.grad_scale = 1.0
-        self.group_lr = dict(group_lr or {})
-        self.pipeline, self.res_calls, self.pair_bwd = False, [], False
         self.lay = VM.VitLayout(answer_spaces)
         sd = {k: np.asarray(v) for k, v in state_dict.items()}
         self._frozen = {k: v for k, v in sd.items() if k.startswith("vision_model.")}
-        self._jobs = []
         with torch.cuda.device(self.dev):
             self._alloc_params(sd)
             self._alloc_vit(sd)
@@ -107,23 +87,16 @@ class VitVQAEngine:
             self._plan_forward()
             self._plan_backward()
             self._plan_optimizer()
-        self.graph = None
-        self._scratch = None
+
+    def _model_specs(self):
+        return VM.model_specs(self.A, self.H)
+
+    def _adam_groups(self):
+        return self.lay.group_of_element(self.group_lr)
 
     # ------------------------------------------------------------------ allocation
     def _alloc_params(self, sd):
-        lay = self.lay
-        self.P32 = torch.from_numpy(lay.pack(sd)).to(self.dev)
-        self.P16 = self.P32.to(BF16)
-        self.G32, self.M, self.V, self.VMAX = (self._t(lay.total, zero=True) for _ in range(4))
-        self.p32, self.p16, self.g32 = {}, {}, {}
-        for s in lay.segments.values():
-            sl = slice(s.offset, s.offset + s.numel)
-            self.p32[s.name] = self.P32[sl].view(s.shape)
-            self.p16[s.name] = self.P16[sl].view(s.shape)
-            self.g32[s.name] = self.G32[sl].view(s.shape)
-        self.opt_state = self._t(L.ST_FLOATS, zero=True)
-        self.RNG = torch.from_numpy(np.array([self.seed & 0xFFFFFFFF, 0, 1, 0], np.uint32).view(np.int32)).to(self.dev)
+        self._alloc_arenas(sd)
         self.bucket_e = torch.from_numpy(t5_bucket_map(self.L, self.L)).reshape(-1).to(self.dev)
         self.bucket_d = torch.from_numpy(VM.causal_bucket_map(self.Ld)).reshape(-1).to(self.dev)
 
@@ -218,21 +191,6 @@ class VitVQAEngine:
         self.WS_HEAD = t(lib.vqa_head_workspace_floats(B, 1, D, self.A))
         self.SQ_PARTS = 1024
         self.WS_SQ = t(self.SQ_PARTS, torch.float64)
-
-    def _nws(self, rows):
-        return self._t(L.load().vqa_norm_bwd_workspace_floats(rows, D))
-
-    def _dw(self, lst, dy16, x16, wname, rows, bias_from=None):
-        """dW[n, k] = dY[rows, n]^T X[rows, k] (+ bias = column sums of dY, deferred)."""
-        g = self.g32[wname]
-        n, k = g.shape
-        self._gemm(lst, dy16, x16, n, k, rows, lda=dy16.shape[-1], ldb=x16.shape[-1], a_trans=True, b_trans=True,
-                   c32=g, ldc32=k)
-        if bias_from is not None:
-            lib = L.load()
-            ws = self._t(lib.vqa_colsum_workspace_floats(rows, n))
-            self._call(lst, "vqa_colsum", bias_from, 1, rows, n, n, None, 0.0, ws)
-            self._defer(ws, lib.vqa_colsum_parts(rows), n, n, self.g32[wname[:-1] + "b"])
 
     # ------------------------------------------------------------------ forward
     def _plan_forward(self):
@@ -362,7 +320,7 @@ class VitVQAEngine:
         self._call(b, "vqa_scatter_rows", self.dANS32, D, self.LASTIDX, 0, 0, self.dDEC32, D, B, D, 4)
         # ---- decoder (reverse): dH32 = gradient of the residual stream, dH16 the FF-branch gradient
         dH32, dR32 = self.dH32_d, self.dR32
-        kp, ws = [], self._nws(TD)
+        kp, ws = [], self._norm_ws(TD)
         self._call(b, "vqa_rmsnorm_bwd", self.dDEC32, self.HS_d[-1], self.RF_d, self.p32["dec.final_ln"], None,
                    dH32, self.dH16[0], None, 0.0, ws, TD, D, self._dptr(SITE_DEC_FINAL, kp), None,
                    self._dptr(dec_site(NL - 1, 5), kp), extra=kp + [self.RNG])
@@ -376,7 +334,7 @@ class VitVQAEngine:
             self._dw(b, dH16[:TD], self.FF_d[i], p + "wo", TD)
             self._dx(b, self.dF16[:TD], p + "wi", TD, out32=self.dC32[:TD])
             self._dw(b, self.dF16[:TD], self.N2_d[i], p + "wi", TD)
-            kp, ws = [], self._nws(TD)
+            kp, ws = [], self._norm_ws(TD)
             self._call(b, "vqa_rmsnorm_bwd", self.dC32, self.HX_d[i], self.R2_d[i], self.p32[p + "ln2"], dH32,
                        self.dX32, self.dB16, None, 0.0, ws, TD, D, None, None, self._dptr(dec_site(i, 3), kp),
                        extra=kp + [self.RNG])
@@ -387,7 +345,7 @@ class VitVQAEngine:
             kp = []
             self._call(b, "vqa_xattn1_bwd", self.dO16, D, None, ops.addr(self.dVALL16, i * D), NL * D, B, Ld, H5, DKV,
                        self._dptr(dec_site(i, 2), kp), extra=kp + [self.dVALL16, self.RNG])
-            kp, ws = [], self._nws(TD)
+            kp, ws = [], self._norm_ws(TD)
             self._call(b, "vqa_rmsnorm_bwd", self.ZERO32, self.HM_d[i], self.R0_d[i], self.p32[p + "ln1"], self.dX32,
                        dR32, self.dB16, None, 0.0, ws, TD, D, None, None, self._dptr(dec_site(i, 1), kp),
                        extra=kp + [self.RNG])
@@ -407,7 +365,7 @@ class VitVQAEngine:
             nxt = self.dH16[1 - cur]
             d32 = self._dptr(SITE_DEC_EMBED, kp) if i == 0 else None
             d16 = self._dptr(dec_site(i - 1, 5), kp) if i > 0 else None
-            ws = self._nws(TD)
+            ws = self._norm_ws(TD)
             self._call(b, "vqa_rmsnorm_bwd", self.dC32, self.HS_d[i], self.R0_d[i], self.p32[p + "ln0"], dR32, dH32,
                        nxt if i > 0 else None, None, 0.0, ws, TD, D, None, d32, d16, extra=kp + [self.RNG])
             self._defer(ws, L.load().vqa_norm_bwd_parts(TD), D, D, self.g32[p + "ln0"])
@@ -434,7 +392,7 @@ class VitVQAEngine:
     def _t5_backward(self, b, ks):
         B, Lq, T = self.B, self.L, self.T
         dH32, dR32 = self.dH32_e, self.dR32
-        kp, ws = [], self._nws(T)
+        kp, ws = [], self._norm_ws(T)
         self._call(b, "vqa_rmsnorm_bwd", self.dTXT32, self.HS_e[-1], self.RF_e, self.p32["enc.final_ln"], None,
                    dH32, self.dH16[0], None, 0.0, ws, T, D, self._dptr(SITE_FINAL, kp), None,
                    self._dptr(t5_site(NL - 1, 3), kp), extra=kp + [self.RNG])
@@ -447,7 +405,7 @@ class VitVQAEngine:
             self._dw(b, dH16[:T], self.FF_e[i], p + "wo", T)
             self._dx(b, self.dF16[:T], p + "wi", T, out32=self.dC32[:T])
             self._dw(b, self.dF16[:T], self.N1_e[i], p + "wi", T)
-            kp, ws = [], self._nws(T)
+            kp, ws = [], self._norm_ws(T)
             self._call(b, "vqa_rmsnorm_bwd", self.dC32, self.HM_e[i], self.R1_e[i], self.p32[p + "ln1"], dH32, dR32,
                        self.dB16, None, 0.0, ws, T, D, None, None, self._dptr(t5_site(i, 1), kp),
                        extra=kp + [self.RNG])
@@ -466,7 +424,7 @@ class VitVQAEngine:
             nxt = self.dH16[1 - cur]
             d32 = self._dptr(SITE_EMBED, kp) if i == 0 else None
             d16 = self._dptr(t5_site(i - 1, 3), kp) if i > 0 else None
-            ws = self._nws(T)
+            ws = self._norm_ws(T)
             self._call(b, "vqa_rmsnorm_bwd", self.dC32, self.HS_e[i], self.R0_e[i], self.p32[p + "ln0"], dR32, dH32,
                        nxt if i > 0 else None, None, 0.0, ws, T, D, None, d32, d16, extra=kp + [self.RNG])
             self._defer(ws, L.load().vqa_norm_bwd_parts(T), D, D, self.g32[p + "ln0"])
@@ -482,43 +440,12 @@ class VitVQAEngine:
         self._call(o, "vqa_grad_sqnorm", self.G32, n, self.WS_SQ, self.SQ_PARTS)
         self._call(o, "vqa_optim_finalize", self.WS_SQ, self.SQ_PARTS, float(self.grad_scale), float(self.max_norm),
                    int(self.warmup), int(self.total), float(self.betas[0]), float(self.betas[1]), self.opt_state)
-        d = L.AdamWDesc()
-        d.param, d.grad = self.P32.data_ptr(), self.G32.data_ptr()
-        d.exp_avg, d.exp_avg_sq, d.max_exp_avg_sq = self.M.data_ptr(), self.V.data_ptr(), self.VMAX.data_ptr()
-        d.param16 = self.P16.data_ptr()
-        d.n = n
-        ends, lrs = self.lay.group_of_element(self.group_lr)
-        d.ngroups = len(ends)
-        for i, (e, lr) in enumerate(zip(ends, lrs)):
-            d.group_end[i], d.group_lr[i] = e, lr
-        d.beta1, d.beta2, d.eps, d.weight_decay = self.betas[0], self.betas[1], self.eps, self.wd
-        d.grad_scale = self.grad_scale
-        d.state = self.opt_state.data_ptr()
-        keep = (self.P32, self.G32, self.M, self.V, self.VMAX, self.P16, self.opt_state)
+        self._adam_desc = self._adam_desc_full()
         # AdamW at the end of the step (a no-op unless the finalize flagged a pending update).
         # Deferring it into the next step beside the frozen ViT, which reads no trained
         # parameter, measured slower (15.1-15.4 vs 14.2 ms per step: HBM / CU contention)
-        o.append(ops.Call("vqa_adamw_amsgrad", ctypes.byref(d), desc=d, keep=keep))
+        o.append(self._adam_call(self._adam_desc))
         self._call(o, "vqa_zero", ops.addr(self.opt_state, L.ST_PENDING), 16, extra=[self.opt_state])
-
-    def configure_optimizer(self, group_lr=None, warmup=None, total=None, max_norm=None, weight_decay=None,
-                            betas=None, eps=None):
-        if group_lr:
-            self.group_lr.update(group_lr)
-        for name, v in (("warmup", warmup), ("total", total)):
-            if v is not None:
-                setattr(self, name, int(v))
-        if max_norm is not None:
-            self.max_norm = float(max_norm)
-        if weight_decay is not None:
-            self.wd = float(weight_decay)
-        if betas is not None:
-            self.betas = tuple(betas)
-        if eps is not None:
-            self.eps = float(eps)
-        self.opt_calls = []
-        self._plan_optimizer()
-        self.graph = None
 
     # ------------------------------------------------------------------ execution
     def load_batch(self, batch):
@@ -531,9 +458,6 @@ class VitVQAEngine:
         load_rows(self.DIDS, batch["decoder_question_input_ids"], n)
         load_rows(self.DMASK, batch["decoder_question_attention_masks"], n)
         load_rows(self.TGT, batch.get("annotation_ids"), n, fill=IGNORE_INDEX)
-
-    def forward(self):
-        self._run(self.fwd_calls)
 
     def forward_with_attentions(self):
         """forward() that also writes the frozen ViT's attention probabilities, HF
@@ -558,12 +482,6 @@ class VitVQAEngine:
             if idx + 1 in at:
                 self._probs_calls[at[idx + 1]](s)
         return tuple(self.ATT_MAPS[i] for i in range(VM.VIT_LAYERS))
-
-    def backward(self):
-        self._run(self.bwd_calls)
-
-    def optimizer_step(self):
-        self._run(self.opt_calls)
 
     def train_step(self):
         if self.graph is not None:
@@ -594,71 +512,6 @@ class VitVQAEngine:
         self.graph = g
 
     # ------------------------------------------------------------------ readouts
-    def forward_backward(self, batch):
-        self.load_batch(batch)
-        self.forward()
-        self.backward()
-        torch.cuda.synchronize(self.dev)
-        return self.LOGP[:self.rows].cpu().numpy(), float(self.LOSS.item())
-
-    def flush_optimizer(self):
-        """Nothing is deferred here: the update runs at the end of the step."""
-
-    def grad_norm(self):
-        return float(self.G32.double().norm())
-
-    def group_grad_norms(self):
-        return {g: float(self.G32[a:e].double().norm()) for g, (a, e) in self.lay.groups.items()}
-
-    def state_dict(self):
-        sd = dict(self._frozen)
-        sd.update(self.lay.unpack(self.P32.cpu().numpy()))
-        return {k: sd[k] for k in VM.model_specs(self.A, self.H)}
-
-    def param_view(self, key):
-        """(parameter, gradient) views of reference entry `key` in the flat arenas (the tied
-        embedding keys all alias the `embed` segment); None for frozen / unknown keys."""
-        specs = VM.model_specs(self.A, self.H)
-        if key in VM.TIED:
-            key = "lang_model.shared.weight"
-        for sg in self.lay.segments.values():
-            if key not in sg.parts:
-                continue
-            p32, g32 = self.p32[sg.name], self.g32[sg.name]
-            row = 0
-            for part in sg.parts:
-                n = specs[part][0]
-                if part == key:
-                    return p32[row:row + n].view(specs[key]), g32[row:row + n].view(specs[key])
-                row += n
-        return None
-
-    def refresh_shadow(self):
-        self.P16.copy_(self.P32)
-
-    def optimizer_state(self):
-        """AdamW(amsgrad) state in reference layout, as VQAEngine.optimizer_state: ({key: exp_avg},
-        {key: exp_avg_sq}, {key: max_exp_avg_sq}, step, dropout RNG) over the trainable keys."""
-        torch.cuda.synchronize(self.dev)
-        unpack = lambda t: {k: v for k, v in self.lay.unpack(t.cpu().numpy()).items() if k not in VM.TIED}  # noqa: E731
-        return (unpack(self.M), unpack(self.V), unpack(self.VMAX), float(self.opt_state[L.ST_STEP].item()),
-                self.RNG.cpu().numpy().copy())
-
-    def load_optimizer_state(self, exp_avg, exp_avg_sq, max_exp_avg_sq, step, rng=None):
-        """Restore what optimizer_state() returned (keys missing from the dicts: zero state)."""
-        specs = VM.model_specs(self.A, self.H)
-        train = [k for s_ in self.lay.segments.values() for k in s_.parts]
-        zeros = {k: np.zeros(specs[k], np.float32) for k in train}
-        for arena, st in ((self.M, exp_avg), (self.V, exp_avg_sq), (self.VMAX, max_exp_avg_sq)):
-            full = dict(zeros)
-            full.update({k: np.asarray(v, np.float32) for k, v in st.items() if k in full})
-            arena.copy_(torch.from_numpy(self.lay.pack(full)))
-        self.opt_state.zero_()
-        self.opt_state[L.ST_STEP] = float(step)
-        if rng is not None:
-            self.RNG.copy_(torch.as_tensor(np.asarray(rng).astype(np.uint32).view(np.int32)))
-        torch.cuda.synchronize(self.dev)
-
     def vit_pooled(self):
         """pooler_output of the frozen ViT for the current batch ([rows, 768], from its bf16 copy)."""
         return self.CAT16[:self.rows, :D].float()

@@ -1,0 +1,35 @@
+"""The engine's plan depends on its arguments and shapes alone: the retired A/B switches
+(VQA_STEM, VQA_RES_FUSE_DS, VQA_EMBED_SPLIT, VQA_EMB_GRID) no longer select anything.  Engines
+are only built here; no step runs."""
+import pytest
+
+RETIRED = {"VQA_STEM": "gemm", "VQA_RES_FUSE_DS": "0", "VQA_EMBED_SPLIT": "0", "VQA_EMB_GRID": "32"}
+
+
+def _engine(pkg, image):
+    sd = _engine.sd = getattr(_engine, "sd", None) or pkg.synthetic.make_state_dict("resnet50", seed=0)
+    return pkg.engine.VQAEngine(sd, vision="resnet50", batch=2, seq_len=16, image_size=image)
+
+
+def _names(eng):
+    return {k: [c.name for c in getattr(eng, k)] for k in ("res_calls", "opt_calls", "tail_calls", "emb_pre")}
+
+
+@pytest.mark.gpu
+def test_plan_ignores_retired_switches_and_stem_follows_the_image_size(pkg, monkeypatch):
+    for k in RETIRED:
+        monkeypatch.delenv(k, raising=False)
+    plain = _names(_engine(pkg, 64))
+    for k, v in RETIRED.items():
+        monkeypatch.setenv(k, v)
+    eng = _engine(pkg, 64)
+    assert _names(eng) == plain
+    # H % 32 == 0: the fused image -> pooled-map stem; the split embedding update with its 256-block grid
+    assert eng.res_calls[0].name == "vqa_stem_pool_img" and eng.IMG8 is None
+    assert eng.embed_split and [c.name for c in eng.emb_pre] == ["vqa_embed_mark", "vqa_adamw_rows"]
+    assert eng.emb_pre[1].args[4] == 256
+    # any other even H (80: a 40 x 40 stem map pooled to 20 x 20): space-to-depth image,
+    # implicit-GEMM stem, max-pool
+    eng = _engine(pkg, 80)
+    assert [c.name for c in eng.res_calls[:3]] == ["vqa_image_to_s2d16", "vqa_gemm", "vqa_maxpool3x3s2_nhwc"]
+    assert tuple(eng.IMG8.shape) == (2, 41, 41, 16)
