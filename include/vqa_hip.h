@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VQA_ABI_VERSION 20
+#define VQA_ABI_VERSION 21
 #define VQA_OK 0
 #define VQA_ERR_INVALID 1000
 
@@ -368,6 +368,14 @@ int vqa_resize_linear_u8(const void* src, const vqa_image_desc* desc, int batch,
  * tokens (slices of 16384, in order); ws = 3*min(tokens, 16384) ints */
 int vqa_embedding_bwd(const long long* ids, const float* dh, float* dtable, int tokens, int d, int vocab, int* ws,
                       hipStream_t stream);
+/* vqa_embedding_bwd's two kernels as calls of their own (ABI 21; tokens <= 16384, one slice):
+ * the sort reads the token ids alone and fills ws (3*tokens ints), so it can run any time after
+ * the ids are known -- the engine's graph step issues it beside the T5 backward, off the step's tail;
+ * the scatter then reads that ws (nothing may write it in between).  vqa_embedding_sort followed
+ * by vqa_embedding_bwd_sorted launches exactly what vqa_embedding_bwd launches. */
+int vqa_embedding_sort(const long long* ids, int tokens, int vocab, int* ws, hipStream_t stream);
+int vqa_embedding_bwd_sorted(const float* dh, float* dtable, int tokens, int d, int vocab, const int* ws,
+                             hipStream_t stream);
 /* zero the dtable rows named by ids_prev[0, tokens) (the rows the previous vqa_embedding_bwd
  * wrote), then ids_prev = ids_cur when ids_cur != NULL: keeps the dense gradient zero outside
  * the touched rows without clearing all vocab*d floats every step */
@@ -384,6 +392,13 @@ int vqa_cast_f32_bf16(const float* x, void* y, long long n, hipStream_t stream);
 int vqa_zero(void* p, long long bytes, hipStream_t stream);
 /* dst <- src, 16-byte aligned (a kernel, so a captured step holds no runtime memcpy node) */
 int vqa_copy(void* dst, const void* src, long long bytes, hipStream_t stream);
+/* up to VQA_COPY_MAX_JOBS such copies in ONE launch (ABI 21; `jobs` is host memory, read before
+ * the call returns; a segment of 0 bytes is skipped): a step's input buffers */
+#define VQA_COPY_MAX_JOBS 8
+typedef struct vqa_copy_job {
+  void* dst; const void* src; long long bytes;     /* 16-byte aligned pointers and size */
+} vqa_copy_job;
+int vqa_copy_multi(const vqa_copy_job* jobs, int njobs, hipStream_t stream);
 /* Tap-shifted copies of an NHWC bf16 map [n, h, w, c] (c % 8 == 0, 16-byte aligned):
  * out[t][(b*h + y)*w + x][:] = in[b][y - ky + pad][x - kx + pad][:] (0 outside), t = ky*kw + kx.
  * The ConvTranspose2d scaler's weight gradient (resnet_vqa_model.py:72-78, 135) as ONE GEMM
@@ -527,6 +542,22 @@ typedef struct vqa_adamw_desc {
 int vqa_grad_sqnorm(const float* g, long long n, double* ws, int parts, hipStream_t stream);
 int vqa_optim_finalize(const double* ws, int parts, float grad_scale, float max_norm, int warmup, int total,
                        float beta1, float beta2, float* state, hipStream_t stream);
+/* The step's last squared-norm work and vqa_optim_finalize in ONE launch (ABI 21): range 0 =
+ * g0[0, n0) and range 1 = g1[0, n1) are summed into ws[fin_parts - 2 parts, fin_parts - parts) and
+ * ws[fin_parts - parts, fin_parts), each exactly as a `parts`-block vqa_grad_sqnorm would; the
+ * workgroup that finishes last (an arrival count in `counter`: a zero-initialised block of
+ * VQA_SQNORM_FINAL_COUNTER_WORDS unsigned words, left at zero) then does what vqa_optim_finalize(ws, fin_parts, ...) does, so partials of earlier
+ * launches in ws[0, fin_parts - 2 parts) are included.  No workgroup waits for another.  Every
+ * partial and the state equal the three separate calls' bit for bit.
+ * mark != NULL: range 1 is `lead` floats read densely, then rows of `cols` floats (the rel-bias
+ * table, then the embedding table); a row r with mark[r] != (int)state[VQA_ST_STEP] is known to
+ * hold exact zeros (no token of the step touched it: vqa_embed_mark + vqa_embedding_zero_rows) and
+ * is not loaded -- its zeros enter the sum in the same places, so the partials do not change. */
+#define VQA_SQNORM_FINAL_COUNTER_WORDS 2112
+int vqa_grad_sqnorm_final(const float* g0, long long n0, const float* g1, long long n1, double* ws, int parts,
+                          int fin_parts, const int* mark, long long lead, int cols, unsigned* counter,
+                          float grad_scale, float max_norm, int warmup, int total, float beta1, float beta2,
+                          float* state, hipStream_t stream);
 int vqa_adamw_amsgrad(const vqa_adamw_desc* d, hipStream_t stream);
 /* The embedding table's AdamW split by rows (ABI 18; the dense table pass was the step's last,
  * exposed 0.9 GB).  vqa_embed_mark: mark[ids[i]] = the step counter (state[VQA_ST_STEP]) for the

@@ -375,6 +375,40 @@ __global__ __launch_bounds__(256) void copy_kernel(uint4* __restrict__ dst, cons
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n16; i += (long)gridDim.x * 256) dst[i] = src[i];
 }
 
+// Up to VQA_COPY_MAX_JOBS copies in one launch: block b serves the segment whose block range
+// holds it (scalar scan, first_block ascending, as colsum_batched_kernel finds its job) and
+// strides over that segment's 16-byte words with the segment's own block count.
+struct CopyMultiArgs {
+  uint4* dst[VQA_COPY_MAX_JOBS];
+  const uint4* src[VQA_COPY_MAX_JOBS];
+  long n16[VQA_COPY_MAX_JOBS];
+  int first_block[VQA_COPY_MAX_JOBS + 1];
+  int njobs;
+};
+__global__ __launch_bounds__(256) void copy_multi_kernel(CopyMultiArgs A) {
+  // constant indices only: a runtime index into the by-value argument block would move it to scratch
+  const int b = (int)blockIdx.x;
+  long n16 = A.n16[0];
+  int b0 = 0, b1 = A.first_block[1];
+  uint4* __restrict__ dst = A.dst[0];
+  const uint4* __restrict__ src = A.src[0];
+#pragma unroll
+  for (int j = 1; j < VQA_COPY_MAX_JOBS; ++j)
+    if (j < A.njobs && A.first_block[j] <= b) {
+      n16 = A.n16[j]; b0 = A.first_block[j]; b1 = A.first_block[j + 1]; dst = A.dst[j]; src = A.src[j];
+    }
+  const long st = (long)(b1 - b0) * 256;
+  long i = (long)(b - b0) * 256 + threadIdx.x;
+  for (; i + 3 * st < n16; i += 4 * st) {                 // four loads in flight per thread
+    uint4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = src[i + u * st];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) dst[i + u * st] = v[u];
+  }
+  for (; i < n16; i += st) dst[i] = src[i];
+}
+
 }  // namespace
 
 extern "C" int vqa_image_to_s2d16(const float* img, void* out, int n, int h, int w, hipStream_t s) {
@@ -479,30 +513,54 @@ extern "C" int vqa_embedding_zero_rows(long long* ids_prev, const long long* ids
   return vqa::check_launch("vqa_embedding_zero_rows");
 }
 
+namespace {
+constexpr int EMB_SLICE = 16384;   // sort keys hold the position in 16 bits; one sort covers this many tokens (128 KiB of LDS)
+
+int launch_embedding_sort(const long long* ids, int n, int vocab, int* ws, hipStream_t s) {
+  if (n <= 1024)
+    hipLaunchKernelGGL(embedding_sort_kernel<1>, dim3(1), dim3(1024), 0, s, ids, n, vocab, ws);
+  else if (n <= 2048)
+    hipLaunchKernelGGL(embedding_sort_kernel<2>, dim3(1), dim3(1024), 0, s, ids, n, vocab, ws);
+  else if (n <= 4096)
+    hipLaunchKernelGGL(embedding_sort_kernel<4>, dim3(1), dim3(1024), 0, s, ids, n, vocab, ws);
+  else if (n <= 8192)
+    hipLaunchKernelGGL(embedding_sort_kernel<8>, dim3(1), dim3(1024), 0, s, ids, n, vocab, ws);
+  else
+    hipLaunchKernelGGL(embedding_sort_kernel<16>, dim3(1), dim3(1024), 0, s, ids, n, vocab, ws);
+  return vqa::check_launch("vqa_embedding_bwd/sort");
+}
+
+int launch_embedding_scatter(const float* dh, float* dtable, int n, int d, const int* ws, hipStream_t s) {
+  hipLaunchKernelGGL(embedding_bwd_kernel, dim3(n, vqa::cdiv(d, 4 * EMB_CL)), dim3(EMB_RL * EMB_CL), 0, s, dh, dtable,
+                     ws, n, d);
+  return vqa::check_launch("vqa_embedding_bwd");
+}
+}  // namespace
+
+// The two halves of vqa_embedding_bwd for one slice (tokens <= 16384): the sort depends on the
+// token ids alone, so a step can run it long before the scatter (the engine: beside the T5 backward).
+extern "C" int vqa_embedding_sort(const long long* ids, int tokens, int vocab, int* ws, hipStream_t s) {
+  VQA_REQUIRE(ids && ws && tokens > 0 && tokens <= EMB_SLICE && vocab > 0,
+              "vqa_embedding_sort: bad arguments (1 <= tokens <= 16384)");
+  return launch_embedding_sort(ids, tokens, vocab, ws, s);
+}
+
+extern "C" int vqa_embedding_bwd_sorted(const float* dh, float* dtable, int tokens, int d, int vocab, const int* ws,
+                                        hipStream_t s) {
+  VQA_REQUIRE(dh && dtable && ws && tokens > 0 && tokens <= EMB_SLICE && d % 4 == 0 && vocab > 0,
+              "vqa_embedding_bwd_sorted: bad arguments (1 <= tokens <= 16384)");
+  return launch_embedding_scatter(dh, dtable, tokens, d, ws, s);
+}
+
 extern "C" int vqa_embedding_bwd(const long long* ids, const float* dh, float* dtable, int tokens, int d, int vocab,
                                  int* ws, hipStream_t s) {
-  // sort keys hold the position in 16 bits; one sort covers <= 16384 tokens (128 KiB of LDS).
   // Larger scatters (DP: world x B x L gathered tokens) run as consecutive slices of 16384
   // tokens in token order, each adding into the rows: deterministic, identical on every rank.
   VQA_REQUIRE(ids && dh && dtable && ws && tokens > 0 && d % 4 == 0, "vqa_embedding_bwd: bad arguments");
-  constexpr int SLICE = 16384;
-  for (int t0 = 0; t0 < tokens; t0 += SLICE) {
-    const int n = tokens - t0 < SLICE ? tokens - t0 : SLICE;
-    const long long* sid = ids + t0;
-    if (n <= 1024)
-      hipLaunchKernelGGL(embedding_sort_kernel<1>, dim3(1), dim3(1024), 0, s, sid, n, vocab, ws);
-    else if (n <= 2048)
-      hipLaunchKernelGGL(embedding_sort_kernel<2>, dim3(1), dim3(1024), 0, s, sid, n, vocab, ws);
-    else if (n <= 4096)
-      hipLaunchKernelGGL(embedding_sort_kernel<4>, dim3(1), dim3(1024), 0, s, sid, n, vocab, ws);
-    else if (n <= 8192)
-      hipLaunchKernelGGL(embedding_sort_kernel<8>, dim3(1), dim3(1024), 0, s, sid, n, vocab, ws);
-    else
-      hipLaunchKernelGGL(embedding_sort_kernel<16>, dim3(1), dim3(1024), 0, s, sid, n, vocab, ws);
-    if (int rc = vqa::check_launch("vqa_embedding_bwd/sort")) return rc;
-    hipLaunchKernelGGL(embedding_bwd_kernel, dim3(n, vqa::cdiv(d, 4 * EMB_CL)), dim3(EMB_RL * EMB_CL), 0, s,
-                       dh + (long long)t0 * d, dtable, ws, n, d);
-    if (int rc = vqa::check_launch("vqa_embedding_bwd")) return rc;
+  for (int t0 = 0; t0 < tokens; t0 += EMB_SLICE) {
+    const int n = tokens - t0 < EMB_SLICE ? tokens - t0 : EMB_SLICE;
+    if (int rc = launch_embedding_sort(ids + t0, n, vocab, ws, s)) return rc;
+    if (int rc = launch_embedding_scatter(dh + (long long)t0 * d, dtable, n, d, ws, s)) return rc;
   }
   return VQA_OK;
 }
@@ -559,6 +617,31 @@ extern "C" int vqa_copy(void* dst, const void* src, long long bytes, hipStream_t
   const int grid = (int)((n16 + 255) / 256 < 8192 ? (n16 + 255) / 256 : 8192);
   hipLaunchKernelGGL(copy_kernel, dim3(grid), dim3(256), 0, s, (uint4*)dst, (const uint4*)src, n16);
   return vqa::check_launch("vqa_copy");
+}
+
+// The step-start input copies as one launch (a launch each cost 5-16 us for KiB-sized buffers).
+extern "C" int vqa_copy_multi(const vqa_copy_job* jobs, int njobs, hipStream_t s) {
+  VQA_REQUIRE(jobs && njobs > 0 && njobs <= VQA_COPY_MAX_JOBS, "vqa_copy_multi: 1..8 jobs");
+  CopyMultiArgs A;
+  int nb = 0, k = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const vqa_copy_job& J = jobs[j];
+    VQA_REQUIRE(J.bytes >= 0 && J.bytes % 16 == 0 && ((uintptr_t)J.dst & 15) == 0 && ((uintptr_t)J.src & 15) == 0 &&
+                    (J.bytes == 0 || (J.dst && J.src)),
+                "vqa_copy_multi: pointers and sizes must be 16-byte aligned");
+    if (J.bytes == 0) continue;                            // an empty segment gets no block
+    const long n16 = (long)(J.bytes / 16);
+    const long blocks = (n16 + 255) / 256 < 4096 ? (n16 + 255) / 256 : 4096;
+    A.dst[k] = (uint4*)J.dst; A.src[k] = (const uint4*)J.src; A.n16[k] = n16; A.first_block[k] = nb;
+    nb += (int)blocks;
+    ++k;
+  }
+  if (k == 0) return VQA_OK;
+  for (int j = k; j <= VQA_COPY_MAX_JOBS; ++j) A.first_block[j] = nb;
+  for (int j = k; j < VQA_COPY_MAX_JOBS; ++j) { A.dst[j] = nullptr; A.src[j] = nullptr; A.n16[j] = 0; }
+  A.njobs = k;
+  hipLaunchKernelGGL(copy_multi_kernel, dim3(nb), dim3(256), 0, s, A);
+  return vqa::check_launch("vqa_copy_multi");
 }
 
 // Tap-shifted copies of an NHWC bf16 map (ConvTranspose2d scaler dW as a tap-batched GEMM):

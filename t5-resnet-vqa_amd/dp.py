@@ -486,7 +486,7 @@ class DataParallelStep:
                                          e.EMB_MARK.data_ptr(), e.opt_state.data_ptr(),
                                          keep=(self.GIDS, e.EMB_MARK, e.opt_state)), e.emb_pre[1]]
                 self.stages[0]["ops"].insert(0, ("emb", self.emb_pre))
-                opt = opt[:2] + list(e.tail_calls)
+                opt = opt[:2] + list(e.tail_calls_unfused)
             a = e._sq_split[1] if e._sq_split is not None else None
             if a is not None:
                 done = 0

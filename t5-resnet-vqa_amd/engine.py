@@ -45,7 +45,8 @@ from . import lib as L
 from . import ops
 from . import synthetic as S
 from .engine_base import (BF16, F32, I64, IGNORE_INDEX, SITE_EMBED, SITE_FINAL, EngineBase, _after,  # noqa: F401
-                          _check_attn_path, _h2d, _Seq, batch_rows, load_rows, no_gc_capture, t5_site)
+                          _check_attn_path, _h2d, _Seq, batch_rows, load_rows, load_rows_multi, no_gc_capture,
+                          t5_site)
 from .layout import ParamLayout, fold_bn, t5_bucket_map
 
 
@@ -89,6 +90,7 @@ class VQAEngine(EngineBase):
         self._rstream_handle = None       # set_res_cumask: the CU-masked ResNet stream ...
         self._rstream_plain = None        # ... and the engine's own, put back by reset_res_cumask
         self.EMB_MARK = None              # row marks of the split embedding update (_plan_optimizer)
+        self.SQ_CNT = None                # arrival counter of vqa_grad_sqnorm_final (_plan_optimizer)
         self.vision, self.B, self.L, self.H = vision, batch, seq_len, image_size
         assert image_size % 2 == 0, "the space-to-depth stem needs an even image size"
         self.NB, self.A = num_blocks, answer_spaces
@@ -1009,6 +1011,37 @@ class VQAEngine(EngineBase):
                             # 6.47-6.48 ms either way), 256 measured 6.44-6.47
                             rows_call(256)]
             self.tail_calls = o[2:-1] + [self.adam_range_call(lay["t5.relbias"].offset, lo), rows_call(1)]
+        # The graph / stream step's shorter tail ("step tail"; needs the row marks):
+        #  * the embedding scatter's id sort runs beside the T5 backward (emb_sort_call; it reads IDS
+        #    alone and nothing else writes WS_EMB), the chain's end keeps the scatter (emb_scatter_call);
+        #  * ONE launch sums the ranges [a, rel-bias) and [rel-bias, n) and finalizes
+        #    (vqa_grad_sqnorm_final); of the table it loads the marked rows only -- every other
+        #    row is exactly zero (vqa_embedding_zero_rows), so the partials are the dense ones.
+        # tail_calls is what that step runs after run_backward_streams; tail_calls_unfused keeps
+        # sqnorm + finalize + the two AdamW parts (dp.DataParallelStep's finish graph, whose
+        # scatter and marks come from the gathered ids).
+        self.tail_calls_unfused = self.tail_calls
+        T = self.T
+        self.fused_tail = self.embed_split and T <= 16384          # one sort slice
+        self.emb_sort_call = self.emb_scatter_call = None
+        if self.fused_tail:
+            if self.SQ_CNT is None:
+                self.SQ_CNT = torch.zeros(L.SQNORM_FINAL_COUNTER_WORDS, dtype=torch.int32,
+                                          device=self.dev)        # arrival counters, left at zero
+            emb = lay["t5.embed"]
+            lead = emb.offset - e0
+            assert lead >= 0 and lead % 4 == 0 and emb.numel == S.T5_VOCAB * self.D and self.D % 4 == 0
+            fin = ops.Call("vqa_grad_sqnorm_final", ops.addr(self.G32, a), e0 - a, ops.addr(self.G32, e0), n - e0,
+                           self.WS_SQ.data_ptr(), K, 3 * K, self.EMB_MARK.data_ptr(), lead, self.D,
+                           self.SQ_CNT.data_ptr(), float(self.grad_scale), float(self.max_norm), int(self.warmup),
+                           int(self.total), float(self.betas[0]), float(self.betas[1]), self.opt_state.data_ptr(),
+                           keep=(self.G32[a:], self.WS_SQ, self.EMB_MARK, self.SQ_CNT, self.opt_state))
+            assert [c.name for c in self.tail_calls[:2]] == ["vqa_grad_sqnorm", "vqa_optim_finalize"]
+            self.tail_calls = [fin] + self.tail_calls[2:]
+            ids, dh, dtab, _, _, _, ws = self.emb_call.args
+            self.emb_sort_call = ops.Call("vqa_embedding_sort", ids, T, S.T5_VOCAB, ws, keep=(self.IDS, self.WS_EMB))
+            self.emb_scatter_call = ops.Call("vqa_embedding_bwd_sorted", dh, dtab, T, self.D, S.T5_VOCAB, ws,
+                                             keep=(self.dH32, self.G32, self.WS_EMB))
 
     def _adam_groups(self):
         ends, lrs = self.lay.group_of_element()
@@ -1034,6 +1067,7 @@ class VQAEngine(EngineBase):
         in one step earlier, or through prime())."""
         ae = self.allow_empty_rows
         n = batch_rows(batch, "question_input_ids", self.B, ae)
+        items = []                                         # (buffer, source, load_rows arguments) of n rows
         if self.pipeline:
             # this batch's images went in one step earlier (or through prime()): their row count
             # must be the text's, else the rows past the shorter one would pair other samples'
@@ -1043,16 +1077,20 @@ class VQAEngine(EngineBase):
                                  f"(loaded one step earlier) had {self._img_rows_next}")
             if next_images is not None:
                 ni = batch_rows({"image_tensors": next_images}, "image_tensors", self.B, ae)
-                load_rows(self.IMG, next_images, ni)
+                if ni == n:
+                    items.append((self.IMG, next_images, {}))
+                else:
+                    load_rows(self.IMG, next_images, ni)
                 self._img_rows_next = ni
             else:
                 self._img_rows_next = None
         else:
-            load_rows(self.IMG, batch["image_tensors"], n)
+            items.append((self.IMG, batch["image_tensors"], {}))
         self.rows = n
-        load_rows(self.IDS, batch["question_input_ids"], n)
-        load_rows(self.MASK, batch["question_attention_masks"], n, empty_fill=1)
-        load_rows(self.TGT, batch.get("annotation_ids"), n, fill=IGNORE_INDEX)
+        items += [(self.IDS, batch["question_input_ids"], {}),
+                  (self.MASK, batch["question_attention_masks"], {"empty_fill": 1}),
+                  (self.TGT, batch.get("annotation_ids"), {"fill": IGNORE_INDEX})]
+        load_rows_multi(items, n)                          # full device batches: one launch for all four
 
     def prime(self, images):
         """Pipelined engines: compute the layer4 features of the first batch's images, so
@@ -1098,10 +1136,14 @@ class VQAEngine(EngineBase):
         the sequential order (and bit-identical: no cross-branch reductions)."""
         self.run_forward_streams()
         if optimizer:
-            self.run_backward_streams(sq_overlap=True)
-            self._run(self.tail_calls)
+            self._backward_and_tail()
         else:
             self.run_backward_streams()
+
+    def _backward_and_tail(self):
+        """The backward and optimizer tail of a full stream / graph step."""
+        self.run_backward_streams(sq_overlap=True, sorted_scatter=self.fused_tail)
+        self._run(self.tail_calls)
 
     def run_forward_streams(self):
         main = torch.cuda.current_stream(self.dev)
@@ -1214,12 +1256,17 @@ class VQAEngine(EngineBase):
         self.clear_pending(hm)                             # the update is applied: once only
         assert set(ev) == set(order)
 
-    def run_backward_streams(self, sq_overlap=False):
+    def run_backward_streams(self, sq_overlap=False, sorted_scatter=False):
         """sq_overlap: also run the optimizer plan's first two calls (the squared-norm partials
         of [0, a), final once the first T5 weight-gradient group is, and of [a, rel-bias),
         final before the embedding scatter) on `side`, beside the backward's tail; the caller
         then runs tail_calls (opt_calls[2:], the embedding table's dense update split by rows:
-        emb_pre runs here, on `side`)."""
+        emb_pre runs here, on `side`).
+        sorted_scatter (the fused tail): the embedding scatter's id sort runs here on `side`, ahead of
+        emb_pre and beside the T5 backward (it reads IDS alone), and the [a, rel-bias) partials are
+        left to the caller's tail_calls (vqa_grad_sqnorm_final) -- the scatter is then the only
+        launch issued behind the chain, beside the trailing weight-gradient GEMMs on `wside`."""
+        assert sq_overlap or not sorted_scatter
         main = torch.cuda.current_stream(self.dev)
         side, wside = self._side, self._wside
         b = self.bwd_calls
@@ -1228,6 +1275,10 @@ class VQAEngine(EngineBase):
         _after(side, main)
         with torch.cuda.stream(side):
             self._run(b[q0:q1])                            # scaler dW / db
+            if sorted_scatter:
+                self.emb_sort_call(L.stream_handle(side))
+                sorted_ev = torch.cuda.Event()
+                sorted_ev.record(side)
             if sq_overlap:                                 # a full step: the untouched embedding rows'
                 self._run(self.emb_pre)                    # update, beside the T5 backward
         if sq_overlap:
@@ -1243,11 +1294,19 @@ class VQAEngine(EngineBase):
                 self._run_tagged(b[q1:m1], main, wside)    # T5 backward up to the first dW group
                 to_side(self.opt_calls[:1])                # grad-norm partials of [0, a), beside the rest
                 self._run_tagged(b[m1:-1], main, wside)
-                to_side(self.opt_calls[1:2])               # ... and of [a, rel-bias)
+                if sorted_scatter:
+                    main.wait_event(sorted_ev)
+                    self._run([self.emb_scatter_call])
+                else:
+                    to_side(self.opt_calls[1:2])           # ... and of [a, rel-bias)
             else:
                 self._run_tagged(b[q1:-1], main, wside)    # T5 backward (+ deferred column sums)
-                to_side(self.opt_calls[:2])
-            self._run(b[-1:])                              # embedding rows
+                if sorted_scatter:
+                    main.wait_event(sorted_ev)
+                    self._run([self.emb_scatter_call])
+                to_side(self.opt_calls[:1] if sorted_scatter else self.opt_calls[:2])
+            if not sorted_scatter:
+                self._run(b[-1:])                          # embedding rows
         else:
             self._run_tagged(b[q1:], main, wside)          # T5 backward + embedding
         for st in (side, wside):
@@ -1337,8 +1396,7 @@ class VQAEngine(EngineBase):
         main = torch.cuda.current_stream(self.dev)
         if self.res_external:                              # the chain only (set_res_cumask)
             self.run_forward_streams()
-            self.run_backward_streams(sq_overlap=True)
-            self._run(self.tail_calls)
+            self._backward_and_tail()
             return
         if not (torch.cuda.is_current_stream_capturing() and self.res_order == "root"):
             self.copy_f4(L.stream_handle(main))            # ("root": issued before the replay, train_step)
@@ -1358,8 +1416,7 @@ class VQAEngine(EngineBase):
         if inter:
             assert not self._res_feed[0], "every ResNet call issued"
             self._res_feed = None
-        self.run_backward_streams(sq_overlap=True)
-        self._run(self.tail_calls)
+        self._backward_and_tail()
         if last:
             with torch.cuda.stream(self._rstream):
                 self._run(self.res_calls)

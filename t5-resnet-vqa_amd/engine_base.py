@@ -132,6 +132,31 @@ def load_rows(dst, src, n, fill=None, empty_fill=0):
         i += k
 
 
+def _plain_device_copy(dst, src):
+    """dst <- src is a plain device copy vqa_copy_multi can take: a contiguous device tensor of the
+    buffer's dtype and size (all planned rows), 16-byte aligned."""
+    return (isinstance(src, torch.Tensor) and src.is_cuda and src.device == dst.device and src.dtype == dst.dtype
+            and src.numel() == dst.numel() and src.is_contiguous() and dst.is_contiguous()
+            and src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0 and (dst.numel() * dst.element_size()) % 16 == 0)
+
+
+def load_rows_multi(items, n):
+    """load_rows for several (dst, src, kwargs) buffers of one batch of n rows.  The full device
+    batches among them (a training loop's usual case: n = the planned rows, sources already on the
+    device in the buffers' dtypes) go in ONE vqa_copy_multi launch on the current stream instead of
+    a runtime copy launch each; anything else keeps load_rows."""
+    jobs = []
+    for dst, src, kw in items:
+        if src is not None and n == dst.shape[0] and len(jobs) < L.COPY_MAX_JOBS and _plain_device_copy(dst, src):
+            jobs.append((dst, src))
+        else:
+            load_rows(dst, src, n, **kw)
+    if jobs:
+        arr = (L.CopyJob * len(jobs))(*[L.CopyJob(d.data_ptr(), s.data_ptr(), d.numel() * d.element_size())
+                                         for d, s in jobs])
+        L.call("vqa_copy_multi", arr, len(jobs))
+
+
 class EngineBase:
     TIED = {}                         # reference keys that alias another trainable key (tied weights)
 

@@ -67,6 +67,15 @@ class ColsumJob(ctypes.Structure):
                 ("beta", c_float), ("first_block", c_int)]
 
 
+class CopyJob(ctypes.Structure):
+    """vqa_copy_job: one segment of vqa_copy_multi."""
+    _fields_ = [("dst", c_void_p), ("src", c_void_p), ("bytes", c_ll)]
+
+
+COPY_MAX_JOBS = 8
+SQNORM_FINAL_COUNTER_WORDS = 2112      # vqa_grad_sqnorm_final's zero-initialised counter block
+
+
 class AttnDesc(ctypes.Structure):
     _fields_ = [
         ("q", c_void_p), ("ldq", c_ll), ("k", c_void_p), ("ldk", c_ll), ("v", c_void_p), ("ldv", c_ll),
@@ -207,6 +216,8 @@ register("vqa_stem_pool_img", P, P, P, P, c_int, c_int)
 register("vqa_colsum", P, c_int, c_int, c_int, c_ll, P, c_float, P)
 register("vqa_embedding_fwd", P, P, P, c_int, c_int, c_int, P)
 register("vqa_embedding_bwd", P, P, P, c_int, c_int, c_int, P)
+register("vqa_embedding_sort", P, c_int, c_int, P)
+register("vqa_embedding_bwd_sorted", P, P, c_int, c_int, c_int, P)
 register("vqa_embedding_zero_rows", P, P, c_int, P, c_int, c_int)
 register("vqa_colsum_batched", P, c_int, c_int)
 register("vqa_t5_relbias_fwd", P, P, P, c_int, c_int, c_int)
@@ -215,6 +226,7 @@ register("vqa_batch_sum", P, c_int, c_ll, P, c_float)
 register("vqa_cast_f32_bf16", P, P, c_ll)
 register("vqa_zero", P, c_ll)
 register("vqa_copy", P, P, c_ll)
+register("vqa_copy_multi", P, c_int)
 register("vqa_tap_shift", P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int)
 register("vqa_quant_rows_fp8", P, c_int, c_ll, c_int, c_int, P, c_ll, P)
 register("vqa_head_fwd", P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int)
@@ -222,6 +234,8 @@ register("vqa_head_bwd", P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int,
 register("vqa_count_targets", P, c_int, P)
 register("vqa_embed_mark", P, c_int, c_int, P, P)
 register("vqa_grad_sqnorm", P, c_ll, P, c_int)
+register("vqa_grad_sqnorm_final", P, c_ll, P, c_ll, P, c_int, c_int, P, c_ll, c_int, P, c_float, c_float, c_int, c_int,
+         c_float, c_float, P)
 register("vqa_vit_patchify", P, P, c_int, c_int, c_int, c_int)
 register("vqa_gather_rows", P, c_ll, P, c_ll, c_ll, P, c_ll, c_int, c_int, c_int)
 register("vqa_scatter_rows", P, c_ll, P, c_ll, c_ll, P, c_ll, c_int, c_int, c_int)
