@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VQA_ABI_VERSION 21
+#define VQA_ABI_VERSION 22
 #define VQA_OK 0
 #define VQA_ERR_INVALID 1000
 
@@ -254,6 +254,22 @@ int vqa_attn_path(const vqa_attn_desc* d, int backward);
  * HF ViTModel(output_attentions=True), the `attentions` that VitVQAModel.generate_answers
  * returns (model/vit_vqa_model.py:238-240, 285-290).  Eval-time readout; o / v / dropout unused. */
 int vqa_attn_probs(const vqa_attn_desc* d, hipStream_t stream);
+/* Attention rollout of a ViT (the reference's heat map, ViT_vqa_heatmap.py:104-137: per image,
+ * mean over the heads of each layer's map, + I, rows divided by their sums, the layers' matrices
+ * chained J_l = A_l J_{l-1}, heat map = J_last[0, 1:]), without the per-head maps.
+ * vqa_attn_headmean: one layer's matrix from its q | k (d: q, k, ldq, ldk, batch, heads,
+ *   lq == lk = n <= 256, dh 64 / 96, scale; operands aligned as for the long forward; no bias or
+ *   key mask; v, o, p, dropout unused):
+ *     aug[(b*n + i)*ld_aug + j] = (mean_h softmax_j(scale q_h,i . k_h,j) + [i == j]) / rowsum,  i, j < n
+ *   ld_aug % 4 == 0, >= n, aug 16-byte aligned; the columns n .. ld_aug-1 are not written.  An
+ *   MFMA kernel, one wave per (image, 32-query block), heads summed in the order 0 .. heads-1.
+ * vqa_rollout_cls: r = row 0 of aug[layers-1][b]; for l = layers-2 .. 0: r <- r aug[l][b]
+ *   (layer l's maps start at aug + l*layer_stride); mask[b*(n-1) + j-1] = r[j], j = 1 .. n-1,
+ *   and, when mask_unit != NULL, mask_unit = mask / max_j mask[b] (the script's mask / mask.max()).
+ *   2 <= n <= 1024.  Neither kernel uses atomics: the results are the same bits on every run. */
+int vqa_attn_headmean(const vqa_attn_desc* d, float* aug, long long ld_aug, hipStream_t stream);
+int vqa_rollout_cls(const float* aug, int layers, int batch, int n, long long ld_aug, long long layer_stride,
+                    float* mask, float* mask_unit, hipStream_t stream);
 
 /* ----------------------------------------------------------------- norms ---
  * Rows of width d (d % 256 == 0, d <= 1024), fp32 in, fp32 and/or bf16 out.

@@ -86,7 +86,6 @@ class VQAEngine(EngineBase):
         # interleave | root; bench.py sets both), and how many of its calls lead an interleave
         self.res_order, self.res_head = "first", 4
         self._res_feed = None             # res_order "interleave": [calls left, stream handle] while a step is issued
-        self._keep_graph = False          # capture(keep_graph=True): the hipGraph_t of each part is kept
         self._rstream_handle = None       # set_res_cumask: the CU-masked ResNet stream ...
         self._rstream_plain = None        # ... and the engine's own, put back by reset_res_cumask
         self.EMB_MARK = None              # row marks of the split embedding update (_plan_optimizer)
@@ -154,7 +153,6 @@ class VQAEngine(EngineBase):
             self._plan_backward()
             self._plan_optimizer()
             self._run(self.quant_all)                     # e4m3 weights of the initial parameters
-        self.eval_call = None            # the evaluation graph's vqa_eval_rows tail (eval_plan)
         self.allreduce = None            # set by the DP trainer: fn(G32 tensor) on the current stream
         self._side = torch.cuda.Stream(self.dev)
         self._wside = torch.cuda.Stream(self.dev)
@@ -1471,9 +1469,6 @@ class VQAEngine(EngineBase):
                 g.instantiate()
         self.graph = parts
 
-    def _new_graph(self):
-        return torch.cuda.CUDAGraph(keep_graph=self._keep_graph)
-
     def _capture_parts(self, s):
         if self.allreduce is None:
             g = self._new_graph()
@@ -1495,63 +1490,12 @@ class VQAEngine(EngineBase):
         return parts
 
     # ------------------------------------------------------------------ evaluation graph
-    # valid_one_epoch / generate_answers of the reference (trainer/faster_rcnn_vqa_trainer.py:
-    # 408-480): the forward in eval mode, top-k of the log-probs and the epoch's loss / accuracy /
-    # WUPS sums, as one replayed forward-only graph ending in vqa_eval_rows.  The graph leaves out
-    # the forward's leading vqa_rng_advance: the reference's model.eval() forward draws no random
-    # numbers, so an evaluation between two training steps must not move the dropout counter.
-    EVAL_CAPACITY = 1 << 16
-
-    def eval_plan(self, topk=5, similarity=None, capacity=None):
-        """Allocate the evaluation outputs -- TOPK_IDX / TOPK_LOGP [B, topk], and one int32 buffer
-        EVAL_BUF = accumulator block (64 bytes) | prediction log | target log, `capacity` rows
-        each -- upload the [A, A] similarity table if one is given, and prepare the
-        vqa_eval_rows call over LOGP / TGT / NLL / LOSS.  Drops an evaluation graph."""
+    # (eval_plan / eval_capture / eval_step / eval_result are EngineBase's; the two hooks are here)
+    def _eval_setup(self, rollout):
         if self.pipeline:
             raise ValueError("pipelined engines take their images a step early; evaluation has no next batch: "
                              "build the engine with pipeline=False to evaluate")
-        if not 1 <= int(topk) <= L.EVAL_MAX_K:
-            raise ValueError(f"topk={topk}: vqa_eval_rows supports 1..{L.EVAL_MAX_K}")
-        capacity = self.EVAL_CAPACITY if capacity is None else int(capacity)
-        if capacity < 0:
-            raise ValueError(f"capacity={capacity} must be >= 0")
-        from .metrics import check_similarity
-        sim = check_similarity(similarity, self.A)
-        k = int(topk)
-        with torch.cuda.device(self.dev):
-            self.TOPK_IDX, self.TOPK_LOGP = self._t((self.B, k), torch.int32, zero=True), self._t((self.B, k), zero=True)
-            self.EVAL_BUF = self._t(16 + 2 * capacity, torch.int32, zero=True)
-            self.EVAL_SIM = None if sim is None else torch.from_numpy(sim).to(self.dev)
-        d = L.EvalDesc()
-        d.logp, d.targets, d.nll, d.loss = (ops.addr(t) for t in (self.LOGP, self.TGT, self.NLL, self.LOSS))
-        d.similarity = ops.addr(self.EVAL_SIM)
-        d.batch, d.answers, d.k = self.B, self.A, k
-        d.topk_idx, d.topk_logp = ops.addr(self.TOPK_IDX), ops.addr(self.TOPK_LOGP)
-        d.acc = ops.addr(self.EVAL_BUF)
-        d.pred_log, d.tgt_log = ops.addr(self.EVAL_BUF, 16), ops.addr(self.EVAL_BUF, 16 + capacity)
-        d.capacity = capacity
-        keep = (self.LOGP, self.TGT, self.NLL, self.LOSS, self.TOPK_IDX, self.TOPK_LOGP, self.EVAL_BUF) + \
-            (() if self.EVAL_SIM is None else (self.EVAL_SIM,))
-        self.eval_call = ops.Call("vqa_eval_rows", ctypes.byref(d), keep=keep, desc=d)
-        self.eval_k, self.eval_capacity = k, capacity
-        self.eval_graph = None
-
-    def eval_prepare(self, topk=5, similarity=None, capacity=None, graph=True):
-        """Make the evaluation plan (and, with `graph`, its graph) match the arguments, reusing
-        what exists: a new table of an engine that already has one is copied into place."""
-        from .metrics import check_similarity
-        sim = check_similarity(similarity, self.A)
-        if capacity is None:                               # keep the planned capacity
-            capacity = self.eval_capacity if self.eval_call is not None else self.EVAL_CAPACITY
-        cap = int(capacity)
-        same = (self.eval_call is not None and self.eval_k == int(topk) and self.eval_capacity == cap
-                and (sim is None) == (self.EVAL_SIM is None))
-        if not same:
-            self.eval_plan(topk, sim, cap)
-        elif sim is not None:
-            _h2d(self.EVAL_SIM, sim)
-        if graph and self.eval_graph is None:
-            self.eval_capture_graph()
+        super()._eval_setup(rollout)
 
     def _run_eval_streams(self):
         """The evaluation step's calls: the forward without its rng advance -- the vision and
@@ -1565,66 +1509,6 @@ class VQAEngine(EngineBase):
         self._forward_branches(main, side, f[p0:p1], f[p1:p2])
         self._run(f[p2:])
         self.eval_call(L.stream_handle(main))
-
-    def eval_capture(self, topk=5, similarity=None, capacity=None):
-        """Plan (eval_plan) and capture the evaluation graph.  The warm-up launch outside the
-        capture leaves RNG, opt_state and the accumulators as it found them.  The training graph
-        is untouched: both live on one engine; configure_optimizer / use_global_rows re-plan
-        calls this graph does not hold."""
-        self.eval_plan(topk, similarity, capacity)
-        self.eval_capture_graph()
-
-    def eval_capture_graph(self):
-        self.flush_optimizer()           # the graph reads the parameters: no update may be pending
-        s = torch.cuda.Stream(self.dev)
-        s.wait_stream(torch.cuda.current_stream(self.dev))
-        saved = (self.opt_state.clone(), self.RNG.clone(), self.EVAL_BUF.clone())
-        with torch.cuda.stream(s):
-            self._run_eval_streams()                    # warm-up launch outside the capture
-        torch.cuda.current_stream(self.dev).wait_stream(s)
-        torch.cuda.synchronize(self.dev)
-        g = self._new_graph()
-        with no_gc_capture():
-            with torch.cuda.graph(g, stream=s):
-                self._run_eval_streams()
-        for dst, src in zip((self.opt_state, self.RNG, self.EVAL_BUF), saved):
-            dst.copy_(src)
-        if self._keep_graph:
-            g.instantiate()
-        self.eval_graph = g
-
-    def eval_step(self, use_graph=True):
-        """Evaluate the loaded batch (load_batch): a pending deferred AdamW update is applied
-        first, the training flag RNG[2] is 0 while the step runs and gets its previous value
-        back (the kernels read it at run time, so one graph serves both modes), and the step
-        adds to the accumulators.  No host sync.  use_graph=False issues the same calls eagerly."""
-        if self.eval_call is None or (use_graph and self.eval_graph is None):
-            raise RuntimeError("eval_step: call eval_capture() (or eval_plan() for use_graph=False) first")
-        self.flush_optimizer()
-        flag = self.RNG[2:3]
-        was = flag.clone()
-        flag.zero_()
-        if use_graph:
-            self.eval_graph.replay()
-        else:
-            self._run_eval_streams()
-        flag.copy_(was)
-
-    def eval_reset(self):
-        """Zero the accumulators and the log cursor (the start of an evaluation epoch)."""
-        self.EVAL_BUF[:16].zero_()
-
-    def eval_result(self):
-        """The epoch's one device -> host read: the accumulator words by name (Python ints and
-        floats) and the logged `predictions` / `targets` of the valid rows, in order, up to the
-        log capacity (cursor > capacity: the rows past it were counted but not logged)."""
-        h = self.EVAL_BUF.cpu().numpy()
-        out = {n: int(v) for n, v in zip(L.EVAL_ACC_INTS, h[:10].view(np.int64))}
-        out.update({n: float(v) for n, v in zip(L.EVAL_ACC_F64, h[10:16].view(np.float64))})
-        n, cap = min(out["cursor"], self.eval_capacity), self.eval_capacity
-        out["predictions"] = h[16:16 + n].tolist()
-        out["targets"] = h[16 + cap:16 + cap + n].tolist()
-        return out
 
     # ------------------------------------------------------------------ readouts (tests / API)
     def _model_specs(self):

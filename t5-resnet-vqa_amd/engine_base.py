@@ -5,6 +5,9 @@ its `keep`), the AdamW descriptors (the full arena and any sub-range of it), the
 forward / backward / optimizer entry points, and the readouts in reference layout
 (state_dict, optimizer state, parameter views).  An engine adds its own plan:
 `_plan_forward` / `_plan_backward` / `_plan_optimizer`, `load_batch`, `train_step`, `capture`.
+The forward-only evaluation graph (eval_plan ... eval_result) is shared too; an engine supplies
+the calls of its evaluation step (`_run_eval_streams`) and says whether it may evaluate
+(`_eval_setup`).
 """
 from __future__ import annotations
 
@@ -171,7 +174,10 @@ class EngineBase:
         self.group_lr = dict(group_lr or {})  # per-group LR overrides (trainer optimizer_kwargs)
         self.fp8 = False                  # e4m3 forward weight GEMMs (VQAEngine, config 5)
         self.graph = None
-        self.eval_graph = None            # a forward-only evaluation graph (VQAEngine.eval_capture)
+        self.eval_graph = None            # a forward-only evaluation graph (eval_capture)
+        self.eval_call = None             # its vqa_eval_rows tail (eval_plan)
+        self.eval_rollout = False         # the evaluation step also carries the attention rollout (VitVQAEngine)
+        self._keep_graph = False          # capture(keep_graph=True): the hipGraph_t of each part is kept
         self._scratch = None              # split-K workspace used while autotuning
         self._jobs = []                   # column-sum reductions queued by _defer until _flush
 
@@ -435,6 +441,139 @@ class EngineBase:
         self.graph = None
         self.eval_graph = None
         return chosen
+
+    # ------------------------------------------------------------------ evaluation graph
+    # valid_one_epoch / generate_answers of the reference (trainer/faster_rcnn_vqa_trainer.py:
+    # 408-480): the forward in eval mode, top-k of the log-probs and the epoch's loss / accuracy /
+    # WUPS sums, as one replayed forward-only graph ending in vqa_eval_rows.  The graph leaves out
+    # the forward's leading vqa_rng_advance: the reference's model.eval() forward draws no random
+    # numbers, so an evaluation between two training steps must not move the dropout counter.
+    EVAL_CAPACITY = 1 << 16
+
+    def _eval_setup(self, rollout):
+        """Hook of eval_plan: raise ValueError if this engine may not evaluate (with `rollout`:
+        with the attention rollout in the step), and prepare what its evaluation step needs
+        beyond the shared vqa_eval_rows tail."""
+        if rollout:
+            raise ValueError("rollout=True: this engine has no attention rollout (VitVQAEngine has)")
+
+    def _run_eval_streams(self):
+        """Hook: issue the evaluation step's calls on the current stream -- the forward without
+        its rng advance, then self.eval_call."""
+        raise NotImplementedError
+
+    def _new_graph(self):
+        return torch.cuda.CUDAGraph(keep_graph=self._keep_graph)
+
+    def eval_plan(self, topk=5, similarity=None, capacity=None, rollout=False):
+        """Allocate the evaluation outputs -- TOPK_IDX / TOPK_LOGP [B, topk], and one int32 buffer
+        EVAL_BUF = accumulator block (64 bytes) | prediction log | target log, `capacity` rows
+        each -- upload the [A, A] similarity table if one is given, and prepare the
+        vqa_eval_rows call over LOGP / TGT / NLL / LOSS.  rollout: the step also computes the
+        attention rollout of its images (VitVQAEngine).  Drops an evaluation graph."""
+        self._eval_setup(bool(rollout))
+        if not 1 <= int(topk) <= L.EVAL_MAX_K:
+            raise ValueError(f"topk={topk}: vqa_eval_rows supports 1..{L.EVAL_MAX_K}")
+        capacity = self.EVAL_CAPACITY if capacity is None else int(capacity)
+        if capacity < 0:
+            raise ValueError(f"capacity={capacity} must be >= 0")
+        from .metrics import check_similarity
+        sim = check_similarity(similarity, self.A)
+        k = int(topk)
+        with torch.cuda.device(self.dev):
+            self.TOPK_IDX, self.TOPK_LOGP = self._t((self.B, k), torch.int32, zero=True), self._t((self.B, k), zero=True)
+            self.EVAL_BUF = self._t(16 + 2 * capacity, torch.int32, zero=True)
+            self.EVAL_SIM = None if sim is None else torch.from_numpy(sim).to(self.dev)
+        d = L.EvalDesc()
+        d.logp, d.targets, d.nll, d.loss = (ops.addr(t) for t in (self.LOGP, self.TGT, self.NLL, self.LOSS))
+        d.similarity = ops.addr(self.EVAL_SIM)
+        d.batch, d.answers, d.k = self.B, self.A, k
+        d.topk_idx, d.topk_logp = ops.addr(self.TOPK_IDX), ops.addr(self.TOPK_LOGP)
+        d.acc = ops.addr(self.EVAL_BUF)
+        d.pred_log, d.tgt_log = ops.addr(self.EVAL_BUF, 16), ops.addr(self.EVAL_BUF, 16 + capacity)
+        d.capacity = capacity
+        keep = (self.LOGP, self.TGT, self.NLL, self.LOSS, self.TOPK_IDX, self.TOPK_LOGP, self.EVAL_BUF) + \
+            (() if self.EVAL_SIM is None else (self.EVAL_SIM,))
+        self.eval_call = ops.Call("vqa_eval_rows", ctypes.byref(d), keep=keep, desc=d)
+        self.eval_k, self.eval_capacity, self.eval_rollout = k, capacity, bool(rollout)
+        self.eval_graph = None
+
+    def eval_prepare(self, topk=5, similarity=None, capacity=None, graph=True, rollout=False):
+        """Make the evaluation plan (and, with `graph`, its graph) match the arguments, reusing
+        what exists: a new table of an engine that already has one is copied into place."""
+        from .metrics import check_similarity
+        sim = check_similarity(similarity, self.A)
+        if capacity is None:                               # keep the planned capacity
+            capacity = self.eval_capacity if self.eval_call is not None else self.EVAL_CAPACITY
+        cap = int(capacity)
+        same = (self.eval_call is not None and self.eval_k == int(topk) and self.eval_capacity == cap
+                and (sim is None) == (self.EVAL_SIM is None) and self.eval_rollout == bool(rollout))
+        if not same:
+            self.eval_plan(topk, sim, cap, rollout)
+        elif sim is not None:
+            _h2d(self.EVAL_SIM, sim)
+        if graph and self.eval_graph is None:
+            self.eval_capture_graph()
+
+    def eval_capture(self, topk=5, similarity=None, capacity=None, rollout=False):
+        """Plan (eval_plan) and capture the evaluation graph.  The warm-up launch outside the
+        capture leaves RNG, opt_state and the accumulators as it found them.  The training graph
+        is untouched: both live on one engine; configure_optimizer / use_global_rows re-plan
+        calls this graph does not hold."""
+        self.eval_plan(topk, similarity, capacity, rollout)
+        self.eval_capture_graph()
+
+    def eval_capture_graph(self):
+        self.flush_optimizer()           # the graph reads the parameters: no update may be pending
+        s = torch.cuda.Stream(self.dev)
+        s.wait_stream(torch.cuda.current_stream(self.dev))
+        saved = (self.opt_state.clone(), self.RNG.clone(), self.EVAL_BUF.clone())
+        with torch.cuda.stream(s):
+            self._run_eval_streams()                    # warm-up launch outside the capture
+        torch.cuda.current_stream(self.dev).wait_stream(s)
+        torch.cuda.synchronize(self.dev)
+        g = self._new_graph()
+        with no_gc_capture():
+            with torch.cuda.graph(g, stream=s):
+                self._run_eval_streams()
+        for dst, src in zip((self.opt_state, self.RNG, self.EVAL_BUF), saved):
+            dst.copy_(src)
+        if self._keep_graph:
+            g.instantiate()
+        self.eval_graph = g
+
+    def eval_step(self, use_graph=True):
+        """Evaluate the loaded batch (load_batch): a pending deferred AdamW update is applied
+        first, the training flag RNG[2] is 0 while the step runs and gets its previous value
+        back (the kernels read it at run time, so one graph serves both modes), and the step
+        adds to the accumulators.  No host sync.  use_graph=False issues the same calls eagerly."""
+        if self.eval_call is None or (use_graph and self.eval_graph is None):
+            raise RuntimeError("eval_step: call eval_capture() (or eval_plan() for use_graph=False) first")
+        self.flush_optimizer()
+        flag = self.RNG[2:3]
+        was = flag.clone()
+        flag.zero_()
+        if use_graph:
+            self.eval_graph.replay()
+        else:
+            self._run_eval_streams()
+        flag.copy_(was)
+
+    def eval_reset(self):
+        """Zero the accumulators and the log cursor (the start of an evaluation epoch)."""
+        self.EVAL_BUF[:16].zero_()
+
+    def eval_result(self):
+        """The epoch's one device -> host read: the accumulator words by name (Python ints and
+        floats) and the logged `predictions` / `targets` of the valid rows, in order, up to the
+        log capacity (cursor > capacity: the rows past it were counted but not logged)."""
+        h = self.EVAL_BUF.cpu().numpy()
+        out = {n: int(v) for n, v in zip(L.EVAL_ACC_INTS, h[:10].view(np.int64))}
+        out.update({n: float(v) for n, v in zip(L.EVAL_ACC_F64, h[10:16].view(np.float64))})
+        n, cap = min(out["cursor"], self.eval_capacity), self.eval_capacity
+        out["predictions"] = h[16:16 + n].tolist()
+        out["targets"] = h[16 + cap:16 + cap + n].tolist()
+        return out
 
     # ------------------------------------------------------------------ readouts (tests / API)
     def forward_backward(self, batch):

@@ -174,6 +174,7 @@ def load():
     lib.vqa_attn_bwd.argtypes = [ctypes.POINTER(AttnDesc), c_void_p]
     lib.vqa_attn_path.argtypes = [ctypes.POINTER(AttnDesc), c_int]
     lib.vqa_attn_probs.argtypes = [ctypes.POINTER(AttnDesc), c_void_p]
+    lib.vqa_attn_headmean.argtypes = [ctypes.POINTER(AttnDesc), c_void_p, c_ll, c_void_p]
     lib.vqa_adamw_amsgrad.argtypes = [ctypes.POINTER(AdamWDesc), c_void_p]
     lib.vqa_eval_rows.argtypes = [ctypes.POINTER(EvalDesc), c_void_p]
     lib.vqa_adamw_rows.argtypes = [ctypes.POINTER(AdamWDesc), c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
@@ -242,6 +243,7 @@ register("vqa_scatter_rows", P, c_ll, P, c_ll, c_ll, P, c_ll, c_int, c_int, c_in
 register("vqa_last_index", P, c_int, c_int, P)
 register("vqa_xattn1_fwd", P, c_ll, P, c_ll, c_int, c_int, c_int, c_int, P)
 register("vqa_xattn1_bwd", P, c_ll, P, P, c_ll, c_int, c_int, c_int, c_int, P)
+register("vqa_rollout_cls", P, c_int, c_int, c_int, c_ll, c_ll, P, P)
 register("vqa_optim_finalize", P, c_int, c_float, c_float, c_int, c_int, c_float, c_float, P)
 
 

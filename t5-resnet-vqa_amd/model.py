@@ -373,6 +373,54 @@ class VitVQAModel:
     def convert_logits_to_predictions(lm_logits):
         return torch.argmax(torch.exp(lm_logits), dim=1)
 
+    def _grid(self, mask):
+        """[n, tokens - 1] -> [n, g, g], g = image_size / 16 (the script's reshape to 14 x 14)."""
+        g = self.image_size // 16
+        return mask.reshape(mask.shape[0], g, g).clone()
+
+    def predict(self, question_input_ids, decoder_question_input_ids, question_attention_masks,
+                decoder_question_attention_masks, pixel_values, annotation_ids=None, topk=5, rollout=False):
+        """The `topk` most probable answers of every row, most probable first (the ViT heat-map
+        script's topk(exp(log-probs), 5), ViT_vqa_heatmap.py): (indices [n, topk] int64, log_probs
+        [n, topk] fp32) for the n real rows, with ResnetVQAModel.predict's contract -- equal
+        log-probs by ascending answer index, the evaluation graph (captured on first use; eval
+        mode, no dropout draw), a short batch padded, labelled rows added to the engine's
+        evaluation accumulators.  rollout=True: the graph also carries the attention rollout of
+        the frozen ViT (the script's heat map before resizing, :104-137) and a third item is
+        returned, mask [n, g, g] fp32 with g = image_size / 16 (not divided by its maximum: see
+        attention_rollout(normalize=True))."""
+        self.load_items({"question_input_ids": question_input_ids, "question_attention_masks": question_attention_masks,
+                         "decoder_question_input_ids": decoder_question_input_ids,
+                         "decoder_question_attention_masks": decoder_question_attention_masks,
+                         "pixel_values": pixel_values, "annotation_ids": annotation_ids})
+        e = self.engine
+        if e.eval_call is None:
+            e.eval_plan(topk, rollout=rollout)
+        elif e.eval_k != int(topk) or e.eval_rollout != bool(rollout):   # re-plan, keeping table and capacity
+            e.eval_plan(topk, e.EVAL_SIM, e.eval_capacity, rollout=rollout)
+        if e.eval_graph is None:
+            e.eval_capture_graph()
+        e.eval_step()
+        out = (e.TOPK_IDX[:e.rows].long(), e.TOPK_LOGP[:e.rows].clone())
+        return out + (self._grid(e.ROLL_MASK[:e.rows]),) if rollout else out
+
+    def attention_rollout(self, question_input_ids, decoder_question_input_ids=None, question_attention_masks=None,
+                          decoder_question_attention_masks=None, annotation_ids=None, pixel_values=None,
+                          image_tensors=None, answer_input_ids=None, answer_attention_masks=None,
+                          question_type_ids=None, normalize=False):
+        """The attention rollout of the batch's images, [n, g, g] fp32 (g = image_size / 16), by the
+        eager forward with the rollout kernels interleaved -- no evaluation plan needed.  Per image
+        (ViT_vqa_heatmap.py:104-137): the head-mean of every ViT layer's attention map, plus the
+        identity, rows divided by their sums; the 12 matrices chained; row 0 without the CLS
+        column.  normalize=True divides each image's map by its maximum (the script's
+        mask / mask.max(); cv2.resize and the colour map stay with the caller)."""
+        self.load_items({"question_input_ids": question_input_ids, "question_attention_masks": question_attention_masks,
+                         "decoder_question_input_ids": decoder_question_input_ids,
+                         "decoder_question_attention_masks": decoder_question_attention_masks,
+                         "pixel_values": pixel_values, "annotation_ids": annotation_ids})
+        mask, unit = self.engine.attention_rollout()
+        return self._grid(unit if normalize else mask)
+
     @staticmethod
     def trainer_group_lr(optimizer_kwargs):
         """vit_vqa_trainer.py:300-316: lang_model at lm_encoder_lr, fusing and classifier layers

@@ -193,15 +193,12 @@ class VQATrainer:
           steps, rows    batches with a labelled row, labelled rows
         Rows without a valid annotation id (padding, unlabelled) count nowhere.  The model's
         train / eval mode is restored.  use_graph=False issues the same calls eagerly
-        (debugging, A/B).  Data parallel: each rank evaluates the batches it is given and returns
+        (debugging, A/B).  Both models' engines evaluate (EngineBase.eval_prepare).  Data parallel: each rank evaluates the batches it is given and returns
         its own figures; no collective runs here."""
         from .metrics import check_similarity
         m = self.model
         sim = check_similarity(similarity, int(m.answer_spaces))    # before any device work
         e = m.engine
-        if not hasattr(e, "eval_prepare"):
-            raise NotImplementedError("evaluate: the evaluation graph is planned for ResnetVQAModel's engine; "
-                                      "use valid_one_epoch for this model")
         was = m.training
         m.eval()
         try:

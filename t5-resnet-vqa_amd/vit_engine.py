@@ -30,7 +30,10 @@ the fusing layer); the oracle (oracle/vit_oracle.py) restates the same sites.
 This module holds the config-4 plan only: the frozen-ViT weights, the activations, the
 forward / backward / optimizer schedules, batch loading, the single-stream step and its
 capture.  Arenas, call builders, the AdamW descriptor, the tuner entry and the state-dict /
-optimizer-state readouts are inherited from engine_base.EngineBase.
+optimizer-state readouts, and the evaluation graph (eval_plan ... eval_result) are inherited from
+engine_base.EngineBase; the evaluation step here is the forward without its rng advance on one
+stream, optionally with the attention rollout of the frozen ViT (vqa_attn_headmean after every
+layer's q|k|v projection, one vqa_rollout_cls: the reference's ViT_vqa_heatmap.py:104-137).
 """
 from __future__ import annotations
 
@@ -195,7 +198,7 @@ class VitVQAEngine(EngineBase):
     # ------------------------------------------------------------------ forward
     def _plan_forward(self):
         f = self.fwd_calls
-        self._vit_attn_at, self.ATT_MAPS, self._probs_calls = [], None, None
+        self._vit_attn_at, self.ATT_MAPS, self._probs_calls, self._roll_calls = [], None, None, None
         B, Lq, Ld, T, TD, TV, NV = self.B, self.L, self.Ld, self.T, self.TD, self.TV, self.NV
         vw = self.vw
         if self.p_drop > 0.0:
@@ -482,6 +485,71 @@ class VitVQAEngine(EngineBase):
             if idx + 1 in at:
                 self._probs_calls[at[idx + 1]](s)
         return tuple(self.ATT_MAPS[i] for i in range(VM.VIT_LAYERS))
+
+    # ------------------------------------------------------------------ attention rollout
+    # The heat map of the reference's ViT script (ViT_vqa_heatmap.py:104-137) from each layer's
+    # q | k, without the [12, B, 12, NV, NV] maps: vqa_attn_headmean after every layer's q|k|v
+    # projection writes (mean over heads + I) / rowsum into ROLL_A[i] ([B, NV, ld] fp32, ld = NV
+    # rounded up to 4), one vqa_rollout_cls after the forward chains row 0 through the layers.
+    def _rollout_plan(self):
+        """The rollout's prepared calls (12 head-mean calls, the chain); buffers on first use."""
+        if self._roll_calls is None:
+            B, NV = self.B, self.NV
+            if NV > 256:
+                raise ValueError(f"attention rollout: {NV} tokens; vqa_attn_headmean supports up to 256 "
+                                 f"(image_size <= {15 * VM.VIT_PATCH})")
+            ld = (NV + 3) // 4 * 4
+            with torch.cuda.device(self.dev):
+                self.ROLL_A = self._t((VM.VIT_LAYERS, B, NV, ld))
+                self.ROLL_MASK, self.ROLL_UNIT = self._t((B, NV - 1)), self._t((B, NV - 1))
+            q = self.VQKV16
+            hm = []
+            for i in range(VM.VIT_LAYERS):
+                d = L.AttnDesc()
+                d.q, d.ldq, d.k, d.ldk = ops.addr(q), 3 * D, ops.addr(q, D), 3 * D
+                d.batch, d.heads, d.lq, d.lk, d.dh, d.scale = B, VM.VIT_HEADS, NV, NV, VM.VIT_DH, VM.VIT_DH ** -0.5
+                hm.append(ops.Call("vqa_attn_headmean", ctypes.byref(d), ops.addr(self.ROLL_A[i]), ld, desc=d,
+                                   keep=(q, self.ROLL_A)))
+            chain = ops.Call("vqa_rollout_cls", ops.addr(self.ROLL_A), VM.VIT_LAYERS, B, NV, ld, B * NV * ld,
+                             ops.addr(self.ROLL_MASK), ops.addr(self.ROLL_UNIT),
+                             keep=(self.ROLL_A, self.ROLL_MASK, self.ROLL_UNIT))
+            self._roll_calls = (hm, chain)
+        return self._roll_calls
+
+    def _forward_rollout(self, start=0):
+        """fwd_calls[start:] with layer i's head-mean call behind its attention, then the chain."""
+        hm, chain = self._rollout_plan()
+        s = L.stream_handle()
+        at = {k: i for i, k in enumerate(self._vit_attn_at)}
+        for idx in range(start, len(self.fwd_calls)):
+            self.fwd_calls[idx](s)
+            if idx + 1 in at:
+                hm[at[idx + 1]](s)
+        chain(s)
+
+    def attention_rollout(self):
+        """forward() that also computes the attention rollout of the loaded images: (mask,
+        mask_unit), each [rows, NV - 1] fp32 -- row 0 of the chained maps without the CLS column,
+        and the same divided by its maximum (the script's mask / mask.max()).  The views are
+        overwritten by the next rollout."""
+        self._forward_rollout()
+        return self.ROLL_MASK[:self.rows], self.ROLL_UNIT[:self.rows]
+
+    # ------------------------------------------------------------------ evaluation (EngineBase's hooks)
+    def _eval_setup(self, rollout):
+        if rollout:
+            self._rollout_plan()
+
+    def _run_eval_streams(self):
+        """The evaluation step on one stream: the forward without its leading vqa_rng_advance
+        (an evaluation does not move the dropout counter), with the rollout's calls when the plan
+        carries them, then vqa_eval_rows."""
+        start = 1 if self.p_drop > 0.0 else 0
+        if self.eval_rollout:
+            self._forward_rollout(start)
+        else:
+            self._run(self.fwd_calls[start:])
+        self.eval_call(L.stream_handle())
 
     def train_step(self):
         if self.graph is not None:
