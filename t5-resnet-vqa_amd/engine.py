@@ -25,12 +25,17 @@ Design (MI355X-first, not a translation of eager PyTorch):
     (include/vqa_hip.h "dropout"); the backward regenerates the masks, nothing
     is stored.  dropout=0 gives eval-mode numerics (golden-vector parity).
 
-This module holds what is the ResNet engine's own: the frozen-ResNet plan, the T5-encoder /
-SGA / head forward and backward plans (fused norms, fp8, batched weight gradients), the
-deferred and row-split optimizer plan, the stream schedule of the step, graph capture and
-the evaluation graph.  The arenas, the call builders, the AdamW descriptors and the
-state-dict / optimizer-state readouts are engine_base.EngineBase's, shared with
-vit_engine.VitVQAEngine; the GEMM tuner is tune.py.
+This module holds what is the ResNet engine's own: the frozen-ResNet plan, the SGA / head
+forward and backward plans (fused norms, fp8, batched weight gradients), the deferred and
+row-split optimizer plan, the stream schedule of the step, graph capture and the evaluation
+graph.  The T5 encoder is planned by t5_stack.T5Stack, the plan the ViT engine's stacks use
+too; what this engine adds to it is its own: activations stacked per layer and one gradient slot
+per layer, so that the weight gradients run per group of layers as batched launches on the side
+stream (t5_dw_group, _t5_group_dw; t5_dw_groups is its one form: the list of group sizes, or
+None for paired dX + dW per layer), the ready marks between groups, and opt-in fuse_norm.  The
+arenas, the call builders, the AdamW descriptors and the state-dict / optimizer-state readouts
+are engine_base.EngineBase's, shared with vit_engine.VitVQAEngine; the GEMM tuner is tune.py.
+The C ABI stays at 22: the shared plan issues the calls the three plans issued.
 """
 from __future__ import annotations
 
@@ -48,6 +53,7 @@ from .engine_base import (BF16, F32, I64, IGNORE_INDEX, SITE_EMBED, SITE_FINAL, 
                           _check_attn_path, _h2d, _Seq, batch_rows, load_rows, load_rows_multi, no_gc_capture,
                           t5_site)
 from .layout import ParamLayout, fold_bn, t5_bucket_map
+from .t5_stack import T5Grads, T5Stack
 
 
 def sga_site(block, kind):
@@ -122,13 +128,17 @@ class VQAEngine(EngineBase):
         # backward runs, and the last, exposed bucket is one layer.
         if t5_dw_group is None:
             t5_dw_group = (3 * self.nl // 4, self.nl - 3 * self.nl // 4)
+        # Kept in one form: the list of group sizes (a size G: [G, G, ..., remainder]), or None
+        # for the paired per-layer form.
         if isinstance(t5_dw_group, (list, tuple)):
             self.t5_dw_groups = [int(x) for x in t5_dw_group]
-            self.t5_dw_group = self.nl
-            assert sum(self.t5_dw_groups) == self.nl and min(self.t5_dw_groups) >= 1
-        else:
+        elif int(t5_dw_group) == 1:
             self.t5_dw_groups = None
-            self.t5_dw_group = int(t5_dw_group)
+        else:
+            G = int(t5_dw_group)
+            assert G > 1, "t5_dw_group: a group size >= 1 or a sequence of sizes"
+            self.t5_dw_groups = [G] * (self.nl // G) + [self.nl % G] * (self.nl % G > 0)
+        assert self.t5_dw_groups is None or (sum(self.t5_dw_groups) == self.nl and min(self.t5_dw_groups) >= 1)
         # SGA blocks' q2 / m2 / fc1 / fc2 weight gradients batched over the blocks
         self.sga_dw_batch = bool(sga_dw_batch)
         # the SGA blocks' self-attentions as ONE launch forward and ONE backward
@@ -336,25 +346,11 @@ class VQAEngine(EngineBase):
         self.TGT = t((B,), I64, zero=True)
         # vision tokens
         self.VIS32, self.VIS16 = t((V, D)), t((V, D), BF16)
-        # T5
-        nl = self.nl
-        self.PB = t((self.h5, Lq, Lq))
-        self.HS = [t((T, D)) for _ in range(nl + 1)]
-        # GEMM inputs the weight gradients read, stacked in backward order (slot = 11 - layer) so
-        # a group of consecutive layers' dW is one batched launch with constant strides
-        self.N0S, self.OS, self.N1S = t((nl, T, D), BF16), t((nl, T, D), BF16), t((nl, T, D), BF16)
-        self.FFS = t((nl, T, self.dff), BF16)
-        self.N0 = [self.N0S[nl - 1 - i] for i in range(nl)]
-        self.QKV = [t((T, 3 * D), BF16) for _ in range(nl)]
-        self.PT = [t((B, self.h5, Lq, Lq)) for _ in range(nl)]
-        self.O = [self.OS[nl - 1 - i] for i in range(nl)]
-        self.HM = [t((T, D)) for _ in range(nl)]
-        self.N1 = [self.N1S[nl - 1 - i] for i in range(nl)]
-        self.FF = [self.FFS[nl - 1 - i] for i in range(nl)]
-        self.R0 = [t(T) for _ in range(nl)]
-        self.R1 = [t(T) for _ in range(nl)]
-        self.RF = t(T)
-        self.TXT32, self.TXT16 = t((T, D)), t((T, D), BF16)
+        # T5 encoder: the GEMM inputs its weight gradients read are stacked in backward order (slot =
+        # 11 - layer) so a group of consecutive layers' dW is one batched launch with constant strides
+        self.t5 = T5Stack(self, "t5.", T, Lq, self.nl, self.h5, self.dkv, self.dff, D, self.IDS, self.MASK,
+                          self.bucket, t5_site, (2, 3), SITE_EMBED, SITE_FINAL, embed="t5.embed", stacked=True)
+        self.TXT32, self.TXT16 = self.t5.OUT32, self.t5.OUT16
         # SGA blocks; the self-attention halves of all blocks share batched buffers:
         # q|k|v of block n in columns [n*2304, (n+1)*2304) of QKV1A, merge in/out in [n]
         self.QKV1A = t((T, NB * 3 * D), BF16)
@@ -405,8 +401,6 @@ class VQAEngine(EngineBase):
         self.dVIS9 = t((9, V, D), BF16)                 # its 3x3 tap-shifted copies (scaler dW)
         self.dH32 = t((T, D))
         self.dHM32 = t((T, D))
-        self.dPB = t((self.h5, Lq, Lq), zero=True)
-        self.dSB = t((self.nl, B, self.h5, Lq, Lq))   # per-layer, per-sample attention dS (rel-bias grad)
         self.WS_EMB = t(3 * T, torch.int32)
         lib = L.load()
         self.WS_COL2 = t(lib.vqa_colsum_workspace_floats(V, D))
@@ -466,32 +460,10 @@ class VQAEngine(EngineBase):
         self._call(lst, "vqa_quant_rows_fp8", x16, 1, k, rows, k, x8, k, xs)
         return x8, xs
 
-    def _rms_kw(self, w, y16, rstd, ws, y32=None, drop=None):
-        """ops.gemm_desc keywords of a T5 RMSNorm fused behind the GEMM that writes its input."""
-        kw = dict(norm=L.NORM_RMS, norm_w=w, norm_eps=1e-6, norm_y32=y32, norm_y16=y16, norm_rstd=rstd, workspace=ws)
-        d = self._drop(drop) if drop is not None else None
-        if d is not None:
-            kw.update(norm_drop=d, keep=(self.RNG,))
-        return kw
-
     def _ln_kw(self, g, b, y32, y16, mean, rstd, ws, **strides):
-        """... of an SGA LayerNorm."""
+        """ops.gemm_desc keywords of an SGA LayerNorm fused behind the GEMM that writes its input."""
         return dict(norm=L.NORM_LAYER, norm_w=g, norm_b=b, norm_eps=1e-5, norm_y32=y32, norm_y16=y16, norm_mean=mean,
                     norm_rstd=rstd, workspace=ws, **strides)
-
-    def _dxdw(self, lst, dy16, x16, wname, rows, bias_from=None, **dxkw):
-        """A layer's input gradient and weight gradient (they share dY) as ONE paired
-        launch (vqa_gemm_pair), then the bias column sum."""
-        tmp = []
-        self._dx(tmp, dy16, wname, rows, **dxkw)
-        self._dw(tmp, dy16, x16, wname, rows, bias_from=bias_from)
-        if not self.pair_bwd:
-            lst.extend(tmp)
-            return
-        gx, gw = tmp[0], tmp[1]
-        lst.append(ops.Call("vqa_gemm_pair", ctypes.byref(gx.desc), ctypes.byref(gw.desc), keep=gx.keep + gw.keep,
-                            desc=(gx.desc, gw.desc)))
-        lst.extend(tmp[2:])
 
     def _gbuf(self, name, shape):
         """A bf16 backward buffer private to one use (see _plan_backward)."""
@@ -523,42 +495,8 @@ class VQAEngine(EngineBase):
         self.sga_vision_calls = [f[-1]]                    # SGA work outside the fusion segment (bench)
         # T5 encoder (independent of the vision branch until the SGA blocks)
         self._fsplit.append(len(f))
-        kp = []
-        self._call(f, "vqa_embedding_fwd", self.IDS, self.p32["t5.embed"], self.HS[0], T, D, S.T5_VOCAB,
-                   self._dptr(SITE_EMBED, kp), extra=kp + [self.RNG])
-        self._call(f, "vqa_t5_relbias_fwd", self.p32["t5.relbias"], self.bucket, self.PB, self.h5, Lq, Lq)
-        self._t5_layer_start = []
-        for i in range(self.nl):
-            self._t5_layer_start.append(len(f))
-            if i == 0 or not fuse:                           # fused: the previous layer's wo wrote N0 / R0
-                self._call(f, "vqa_rmsnorm_fwd", self.HS[i], self.p32[f"t5.{i}.ln0"], None, self.N0[i], self.R0[i],
-                           T, D, 1e-6, None)
-            self._linear(f, self.N0[i], f"t5.{i}.qkv_w", T, out16=self.QKV[i], bias=False)
-            q = self.QKV[i]
-            self._attn(f, "vqa_attn_fwd", q=q, ldq=3 * D, k=ops.addr(q, D), ldk=3 * D, v=ops.addr(q, 2 * D),
-                       ldv=3 * D, o=self.O[i], ldo=D, p=self.PT[i], bias=self.PB, key_mask=self.MASK, batch=B,
-                       heads=self.h5, lq=Lq, lk=Lq, dh=self.dkv, scale=1.0, drop=t5_site(i, 0))
-            # h + dropout(attention output)   (T5LayerSelfAttention :400)
-            self._linear(f, self.O[i], f"t5.{i}.o_w", T, out32=self.HM[i], bias=False, res32=self.HS[i],
-                         drop=t5_site(i, 1),
-                         norm=self._rms_kw(self.p32[f"t5.{i}.ln1"], self.N1[i], self.R1[i], wt5) if fuse else None)
-            # dropout(relu(wi h)) (T5DenseActDense :86), then h + dropout(wo .) (T5LayerFF :140)
-            if not fuse:
-                self._call(f, "vqa_rmsnorm_fwd", self.HM[i], self.p32[f"t5.{i}.ln1"], None, self.N1[i], self.R1[i],
-                           T, D, 1e-6, None)
-            self._linear(f, self.N1[i], f"t5.{i}.wi", T, out16=self.FF[i], bias=False, relu=True,
-                         drop=t5_site(i, 2))
-            nrm = None
-            if fuse and i + 1 < self.nl:                     # wo carries the next layer's ln0 ...
-                nrm = self._rms_kw(self.p32[f"t5.{i + 1}.ln0"], self.N0[i + 1], self.R0[i + 1], wt5)
-            elif fuse:                                       # ... the last one the final norm and its dropout
-                nrm = self._rms_kw(self.p32["t5.final_ln"], self.TXT16, self.RF, wt5, y32=self.TXT32, drop=SITE_FINAL)
-            self._linear(f, self.FF[i], f"t5.{i}.wo", T, out32=self.HS[i + 1], bias=False, res32=self.HM[i],
-                         drop=t5_site(i, 3), norm=nrm)
-        if not fuse:
-            kp = []
-            self._call(f, "vqa_rmsnorm_fwd", self.HS[-1], self.p32["t5.final_ln"], self.TXT32, self.TXT16, self.RF, T,
-                       D, 1e-6, self._dptr(SITE_FINAL, kp), extra=kp + [self.RNG])
+        self.t5.plan_forward(self, f, fuse=wt5)
+        self._t5_layer_start = self.t5.layer_start
         self._fsplit.append(len(f))
         # SGA blocks: x = text always, y chained
         y16 = self.VIS16
@@ -699,7 +637,7 @@ class VQAEngine(EngineBase):
         # batched over the blocks (the block chain then runs its input gradients alone)
         self.dA3S, self.dBS, self.dA2S, self.dQS = (self._t((NB, T, D), BF16) for _ in range(4))
         batched = self.sga_dw_batch
-        dxdw = (lambda lst, dy, x, w, rows, **kw: self._dx(lst, dy, w, rows, **kw)) if batched else self._dxdw
+        dxdw = self._dx_only if batched else self._dxdw
         for n in reversed(range(NB)):
             s, p = self.sga[n], f"sga{n}."
             dy = self.dY[n & 1]
@@ -824,70 +762,25 @@ class VQAEngine(EngineBase):
         # per-layer bf16 gradients the weight gradients read, stacked like the inputs (slot 11 - i)
         self.dH16S, self.dHMS = self._t((nl, T, D), BF16), self._t((nl, T, D), BF16)
         self.dFS, self.dQKVS = self._t((nl, T, self.dff), BF16), self._t((nl, T, 3 * D), BF16)
-        dH16 = [self.dH16S[nl - 1 - i] for i in range(nl)]               # FF-branch grad of layer i
-        G = self.t5_dw_group
-        kp = []
-        ws = self._norm_ws()
-        self._call(b, "vqa_rmsnorm_bwd", self.dTXT, self.HS[-1], self.RF, self.p32["t5.final_ln"], None, self.dH32,
-                   dH16[-1], None, 0.0, ws, T, D,
-                   self._dptr(SITE_FINAL, kp), None, self._dptr(t5_site(self.nl - 1, 3), kp),
-                   extra=kp + [self.RNG])
-        self._defer(ws, nparts, D, D, self.g32["t5.final_ln"])
-        mark("t5.final_ln")
-        # G > 1: the layers' input gradients chain alone and every G layers ONE batched launch
-        # per weight (wo, wi, o, qkv) computes the group's weight gradients (4 x G GEMMs of
-        # K = 2048 as 4 launches); G == 1: each layer's dX + dW as paired launches
-        dxdw = self._dxdw if (G == 1 and not self.t5_dw_groups) else \
-            (lambda lst, dy, x, w, rows, **kw: self._dx(lst, dy, w, rows, **kw))
-        for i in reversed(range(nl)):
-            dF, dHM, dQKV = self.dFS[nl - 1 - i], self.dHMS[nl - 1 - i], self.dQKVS[nl - 1 - i]
-            dxdw(b, dH16[i], self.FF[i], f"t5.{i}.wo", T, out16=dF, mask16=self.FF[i], alpha=ks)
-            dxdw(b, dF, self.N1[i], f"t5.{i}.wi", T, out32=self.dC32)
-            kp = []
-            ws = self._norm_ws()
-            self._call(b, "vqa_rmsnorm_bwd", self.dC32, self.HM[i], self.R1[i], self.p32[f"t5.{i}.ln1"], self.dH32,
-                       self.dHM32, dHM, None, 0.0, ws, T, D,
-                       None, None, self._dptr(t5_site(i, 1), kp), extra=kp + [self.RNG])
-            self._defer(ws, nparts, D, D, self.g32[f"t5.{i}.ln1"])
-            dxdw(b, dHM, self.O[i], f"t5.{i}.o_w", T, out16=self.dO16)
-            q = self.QKV[i]
-            dq = dQKV
-            self._attn(b, "vqa_attn_bwd", q=q, ldq=3 * D, k=ops.addr(q, D), ldk=3 * D, v=ops.addr(q, 2 * D),
-                       ldv=3 * D, p=self.PT[i], bias=self.PB, key_mask=self.MASK, batch=B, heads=self.h5, lq=Lq,
-                       lk=Lq, dh=self.dkv, scale=1.0, dout=self.dO16, lddo=D, dq=dq, lddq=3 * D,
-                       dk=ops.addr(dq, D), lddk=3 * D, dv=ops.addr(dq, 2 * D), lddv=3 * D, dbias=self.dSB[i],
-                       drop=t5_site(i, 0))
-            dxdw(b, dq, self.N0[i], f"t5.{i}.qkv_w", T, out32=self.dC32)
-            # layer 0: dH32 becomes the embedding gradient (masked by the embedding dropout :725);
-            # otherwise dH16 is the FF branch gradient of layer i-1
-            kp = []
-            d32 = self._dptr(SITE_EMBED, kp) if i == 0 else None
-            d16 = self._dptr(t5_site(i - 1, 3), kp) if i > 0 else None
-            ws = self._norm_ws()
-            self._call(b, "vqa_rmsnorm_bwd", self.dC32, self.HS[i], self.R0[i], self.p32[f"t5.{i}.ln0"], self.dHM32,
-                       self.dH32, dH16[i - 1] if i > 0 else None, None, 0.0, ws, T, D,
-                       None, d32, d16, extra=kp + [self.RNG])
-            self._defer(ws, nparts, D, D, self.g32[f"t5.{i}.ln0"])
-            done = nl - i                                   # layers finished so far (11 .. i)
-            ends = (np.cumsum(self.t5_dw_groups) if self.t5_dw_groups else None)
-            if G == 1 and ends is None:
+        grads = T5Grads(*([s[nl - 1 - i] for i in range(nl)] for s in (self.dH16S, self.dFS, self.dHMS, self.dQKVS)),
+                        self.dTXT, self.dH32, self.dHM32, self.dC32, self.dO16)
+        # grouped: the layers' input gradients chain alone and after every group of layers ONE
+        # batched launch per weight (wo, wi, o, qkv) computes the group's weight gradients (4 x G
+        # GEMMs of K = 2048 as 4 launches); else each layer's dX + dW as paired launches
+        groups = self.t5_dw_groups
+        size_at = {int(e): g for e, g in zip(np.cumsum(groups), groups)} if groups else {}   # layers done -> group
+
+        def after_layer(i):
+            if i == nl:                                     # the final norm
+                mark("t5.final_ln")
+            elif groups is None:
                 mark(f"t5.{i}.ln1")
-            elif ends is not None and done in ends:
-                k = int(np.searchsorted(ends, done))
-                self._t5_group_dw(b, i + self.t5_dw_groups[k] - 1, i)
+            elif nl - i in size_at:
+                self._t5_group_dw(b, i + size_at[nl - i] - 1, i)
                 mark(f"t5.{i}.ln1")
                 if self._sq_split is None and i > 0:      # the first T5 dW group is final
                     self._sq_split = self.ready_marks[-1]
-            elif ends is None and (done % G == 0 or i == 0):
-                self._t5_group_dw(b, i + (done - 1) % G, i)
-                mark(f"t5.{i}.ln1")
-                if self._sq_split is None and i > 0:
-                    self._sq_split = self.ready_marks[-1]
-        # the relative-position bias is shared by all 12 layers: dPB = sum over (layer, sample) of dS,
-        # one fixed-order reduction after the last layer instead of one per layer
-        self._call(b, "vqa_batch_sum", self.dSB, self.nl * B, self.h5 * Lq * Lq, self.dPB, 0.0)
-        self._call(b, "vqa_t5_relbias_bwd", self.dPB, self.bucket, self.g32["t5.relbias"], self.h5, Lq, Lq,
-                   S.T5_BUCKETS)
+        self.t5.plan_backward(self, b, grads, self._dxdw if groups is None else self._dx_only, after_layer)
         mark("t5.relbias")
         self._flush(b)
         # embedding rows last (DP replaces this call by an all-gather of (id, dH row) pairs)
@@ -897,10 +790,10 @@ class VQAEngine(EngineBase):
     def _t5_group_dw(self, lst, i_hi, i_lo):
         """Weight gradients of T5 layers i_hi >= .. >= i_lo: per weight one launch batched over
         the layers (stack slot 11 - i, consecutive gradient segments at a constant stride)."""
-        nl, T = self.nl, self.T
+        nl, T, st = self.nl, self.T, self.t5
         cnt, s0 = i_hi - i_lo + 1, nl - 1 - i_hi
-        for w, dys, xs in (("wo", self.dH16S, self.FFS), ("wi", self.dFS, self.N1S), ("o_w", self.dHMS, self.OS),
-                           ("qkv_w", self.dQKVS, self.N0S)):
+        for w, dys, xs in (("wo", self.dH16S, st.FFS), ("wi", self.dFS, st.N1S), ("o_w", self.dHMS, st.OS),
+                           ("qkv_w", self.dQKVS, st.N0S)):
             nout, kin = self.g32[f"t5.{i_hi}.{w}"].shape
             segs = [self.lay[f"t5.{i}.{w}"] for i in range(i_hi, i_lo - 1, -1)]
             lstride = segs[1].offset - segs[0].offset if cnt > 1 else 0

@@ -7,7 +7,8 @@ forward / backward / optimizer entry points, and the readouts in reference layou
 `_plan_forward` / `_plan_backward` / `_plan_optimizer`, `load_batch`, `train_step`, `capture`.
 The forward-only evaluation graph (eval_plan ... eval_result) is shared too; an engine supplies
 the calls of its evaluation step (`_run_eval_streams`) and says whether it may evaluate
-(`_eval_setup`).
+(`_eval_setup`).  The builders are also what t5_stack.T5Stack, the one plan of a T5 layer stack
+(the ResNet model's encoder, the ViT model's encoder and decoder), appends its calls through.
 """
 from __future__ import annotations
 
@@ -173,6 +174,7 @@ class EngineBase:
         self.grad_scale = grad_scale
         self.group_lr = dict(group_lr or {})  # per-group LR overrides (trainer optimizer_kwargs)
         self.fp8 = False                  # e4m3 forward weight GEMMs (VQAEngine, config 5)
+        self.pair_bwd = False             # _dxdw as one paired launch (VQAEngine)
         self.graph = None
         self.eval_graph = None            # a forward-only evaluation graph (eval_capture)
         self.eval_call = None             # its vqa_eval_rows tail (eval_plan)
@@ -317,6 +319,22 @@ class EngineBase:
         if bias_from is not None:
             assert bias_from.shape[-1] == n
             self._bias_colsum(lst, bias_from, rows, wname[:-1] + "b")
+
+    def _dxdw(self, lst, dy16, x16, wname, rows, bias_from=None, **dxkw):
+        """A layer's input gradient and weight gradient (they share dY), then the bias column
+        sum; with pair_bwd the two GEMMs as ONE paired launch (vqa_gemm_pair)."""
+        tmp = []
+        self._dx(tmp, dy16, wname, rows, **dxkw)
+        self._dw(tmp, dy16, x16, wname, rows, bias_from=bias_from)
+        if self.pair_bwd:
+            gx, gw = tmp[:2]
+            tmp[:2] = [ops.Call("vqa_gemm_pair", ctypes.byref(gx.desc), ctypes.byref(gw.desc), keep=gx.keep + gw.keep,
+                                desc=(gx.desc, gw.desc))]
+        lst.extend(tmp)
+
+    def _dx_only(self, lst, dy16, x16, wname, rows, **dxkw):
+        """_dxdw without the weight gradient (left to a launch batched over layers)."""
+        self._dx(lst, dy16, wname, rows, **dxkw)
 
     def _bias_colsum(self, lst, dy16, rows, bname):
         """A Linear bias gradient = column sums of its bf16 output gradient: the partial

@@ -11,7 +11,7 @@ Forward (:166-225):
     q|k|v GEMM with bias, the long-sequence MFMA attention, output GEMM + residual,
     LayerNorm, GELU GEMM, GEMM + residual); final LayerNorm and tanh pooler on the
     CLS rows only (the pooler reads nothing else);
-  * T5 encoder as in the ResNet path; its CLS rows (encoder_outputs[:, 0, :], :189)
+  * T5 encoder: the ResNet path's plan (t5_stack.T5Stack); its CLS rows (encoder_outputs[:, 0, :], :189)
     and the pooled ViT output are the fusing layer's concat (:192-195);
   * fusing_layer: Linear(1536, 768) + ReLU + Dropout(0.5), one GEMM (:198);
   * T5 decoder (:199-205) over the ONE fused token: causal self-attention with the
@@ -29,8 +29,13 @@ the fusing layer); the oracle (oracle/vit_oracle.py) restates the same sites.
 
 This module holds the config-4 plan only: the frozen-ViT weights, the activations, the
 forward / backward / optimizer schedules, batch loading, the single-stream step and its
-capture.  Arenas, call builders, the AdamW descriptor, the tuner entry and the state-dict /
-optimizer-state readouts, and the evaluation graph (eval_plan ... eval_result) are inherited from
+capture.  The T5 encoder and decoder are two t5_stack.T5Stack, planned by the code that plans
+the ResNet engine's encoder; the decoder's cross-attention sub-layer (_cross_forward /
+_cross_backward) and the one-GEMM value projection stay here.  On purpose, not by omission, the
+two stacks keep in-line weight gradients (_dx then _dw through shared scratch, ping-pong dH16)
+and stand-alone norms: the ResNet engine's grouped weight gradients or fuse_norm would be a
+performance change with measurements of its own.  The C ABI stays at 22.  Arenas, call
+builders, the AdamW descriptor, the tuner entry and the state-dict / optimizer-state readouts, and the evaluation graph (eval_plan ... eval_result) are inherited from
 engine_base.EngineBase; the evaluation step here is the forward without its rng advance on one
 stream, optionally with the attention rollout of the frozen ViT (vqa_attn_headmean after every
 layer's q|k|v projection, one vqa_rollout_cls: the reference's ViT_vqa_heatmap.py:104-137).
@@ -49,6 +54,7 @@ from . import vit_model as VM
 from .engine_base import (BF16, F32, I64, IGNORE_INDEX, SITE_EMBED, SITE_FINAL, EngineBase, batch_rows, load_rows,
                           no_gc_capture, t5_site)
 from .layout import t5_bucket_map
+from .t5_stack import T5Grads, T5Stack
 
 D = S.D_MODEL
 NL, H5, DKV, DFF = S.T5_LAYERS, S.T5_HEADS, S.T5_DKV, S.T5_DFF
@@ -150,26 +156,14 @@ class VitVQAEngine(EngineBase):
         self.VCLS32, self.VCLSN16, self.VCMU, self.VCRS = t((B, D)), t((B, D), BF16), t(B), t(B)
         self.CAT16, self.FUSED16 = t((B, 2 * D), BF16), t((B, D), BF16)
         self.VALL16 = t((B, NL * D), BF16)
-        # T5 encoder
-        self.PB_e = t((H5, Lq, Lq))
-        self.HS_e = [t((T, D)) for _ in range(NL + 1)]
-        self.N0_e, self.O_e, self.N1_e = ([t((T, D), BF16) for _ in range(NL)] for _ in range(3))
-        self.QKV_e = [t((T, 3 * D), BF16) for _ in range(NL)]
-        self.PT_e = [t((B, H5, Lq, Lq)) for _ in range(NL)]
-        self.HM_e = [t((T, D)) for _ in range(NL)]
-        self.FF_e = [t((T, DFF), BF16) for _ in range(NL)]
-        self.R0_e, self.R1_e = [t(T) for _ in range(NL)], [t(T) for _ in range(NL)]
-        self.RF_e, self.TXT32, self.TXT16 = t(T), t((T, D)), t((T, D), BF16)
-        # T5 decoder
-        self.PB_d = t((H5, Ld, Ld))
-        self.HS_d = [t((TD, D)) for _ in range(NL + 1)]
-        self.N0_d, self.O_d, self.CTX_d, self.N2_d = ([t((TD, D), BF16) for _ in range(NL)] for _ in range(4))
-        self.QKV_d = [t((TD, 3 * D), BF16) for _ in range(NL)]
-        self.PT_d = [t((B, H5, Ld, Ld)) for _ in range(NL)]
-        self.HM_d, self.HX_d = [t((TD, D)) for _ in range(NL)], [t((TD, D)) for _ in range(NL)]
-        self.FF_d = [t((TD, DFF), BF16) for _ in range(NL)]
-        self.R0_d, self.R2_d = [t(TD) for _ in range(NL)], [t(TD) for _ in range(NL)]
-        self.RF_d, self.DEC32, self.DEC16 = t(TD), t((TD, D)), t((TD, D), BF16)
+        # T5 encoder and decoder (t5_stack.T5Stack: per-layer activations)
+        self.enc = T5Stack(self, "enc.", T, Lq, NL, H5, DKV, DFF, D, self.IDS, self.MASK, self.bucket_e, t5_site,
+                           (2, 3), SITE_EMBED, SITE_FINAL)
+        self.dec = T5Stack(self, "dec.", TD, Ld, NL, H5, DKV, DFF, D, self.DIDS, self.DMASK, self.bucket_d, dec_site,
+                           (4, 5), SITE_DEC_EMBED, SITE_DEC_FINAL, ff_norm="ln2", decoder=True)
+        self.TXT32, self.TXT16, self.DEC32 = self.enc.OUT32, self.enc.OUT16, self.dec.OUT32
+        # read by tools/vit_trained_diag.py
+        self.HS_d, self.HM_d, self.HX_d, self.O_d = self.dec.HS, self.dec.HM, self.dec.HX, self.dec.O
         # answer gather + head (the pooler of the head kernel over a length-1 sequence: identity)
         self.LASTIDX, self.ANS32 = t(B, I64, zero=True), t((B, D))
         self.DUMMY_PW, self.DUMMY_PB = t(D, zero=True), t(1, zero=True)
@@ -187,8 +181,6 @@ class VitVQAEngine(EngineBase):
         self.dB16, self.dF16, self.dO16 = t((mx, D), BF16), t((mx, DFF), BF16), t((mx, D), BF16)
         self.dQKV16 = t((mx, 3 * D), BF16)
         self.dVALL16, self.dPRE16, self.dCLS32 = t((B, NL * D), BF16), t((B, D), BF16), t((B, D))
-        self.dSB_e, self.dSB_d = t((NL, B, H5, Lq, Lq)), t((NL, B, H5, Ld, Ld))
-        self.dPB_e, self.dPB_d = t((H5, Lq, Lq)), t((H5, Ld, Ld))
         lib = L.load()
         self.WS_EMB = t(3 * min(T + TD, 16384), torch.int32)
         self.WS_HEAD = t(lib.vqa_head_workspace_floats(B, 1, D, self.A))
@@ -199,7 +191,7 @@ class VitVQAEngine(EngineBase):
     def _plan_forward(self):
         f = self.fwd_calls
         self._vit_attn_at, self.ATT_MAPS, self._probs_calls, self._roll_calls = [], None, None, None
-        B, Lq, Ld, T, TD, TV, NV = self.B, self.L, self.Ld, self.T, self.TD, self.TV, self.NV
+        B, Lq, Ld, TV, NV = self.B, self.L, self.Ld, self.TV, self.NV
         vw = self.vw
         if self.p_drop > 0.0:
             self._call(f, "vqa_rng_advance", self.RNG)
@@ -235,12 +227,8 @@ class VitVQAEngine(EngineBase):
         self._gemm(f, self.VCLSN16, vw["pool_w"], B, D, D, lda=D, ldb=D, c16=self.CAT16, ldc16=2 * D,
                    bias=vw["pool_b"], relu=3)
         self.vit_calls = len(f)
-        # ---- T5 encoder (the ResNet path's plan, config-4 arena names)
-        self._t5_forward(f, "enc", self.IDS, self.MASK, T, Lq, self.HS_e, self.N0_e, self.QKV_e, self.PT_e, self.O_e,
-                         self.HM_e, self.N1_e, self.FF_e, self.R0_e, self.R1_e, self.PB_e, self.bucket_e)
-        kp = []
-        self._call(f, "vqa_rmsnorm_fwd", self.HS_e[-1], self.p32["enc.final_ln"], self.TXT32, self.TXT16, self.RF_e,
-                   T, D, 1e-6, self._dptr(SITE_FINAL, kp), extra=kp + [self.RNG])
+        # ---- T5 encoder (the ResNet path's plan: t5_stack.T5Stack)
+        self.enc.plan_forward(self, f)
         # encoder_outputs[:, 0, :] -> right half of the fusing layer's input
         self._call(f, "vqa_gather_rows", self.TXT16, D, None, Lq, 0, ops.addr(self.CAT16, D), 2 * D, B, D, 2,
                    extra=[self.CAT16])
@@ -254,65 +242,26 @@ class VitVQAEngine(EngineBase):
         self._gemm(f, self.FUSED16, self.p16["dec.xv_w"], B, NL * D, D, lda=D, ldb=D, c16=self.VALL16,
                    ldc16=NL * D)
         # ---- T5 decoder
-        kp = []
-        self._call(f, "vqa_embedding_fwd", self.DIDS, self.p32["embed"], self.HS_d[0], TD, D, S.T5_VOCAB,
-                   self._dptr(SITE_DEC_EMBED, kp), extra=kp + [self.RNG])
-        self._call(f, "vqa_t5_relbias_fwd", self.p32["dec.relbias"], self.bucket_d, self.PB_d, H5, Ld, Ld)
-        for i in range(NL):
-            p = f"dec.{i}."
-            self._call(f, "vqa_rmsnorm_fwd", self.HS_d[i], self.p32[p + "ln0"], None, self.N0_d[i], self.R0_d[i],
-                       TD, D, 1e-6, None)
-            self._linear(f, self.N0_d[i], p + "qkv_w", TD, out16=self.QKV_d[i], bias=False)
-            q = self.QKV_d[i]
-            self._attn(f, "vqa_attn_fwd", q=q, ldq=3 * D, k=ops.addr(q, D), ldk=3 * D, v=ops.addr(q, 2 * D),
-                       ldv=3 * D, o=self.O_d[i], ldo=D, p=self.PT_d[i], bias=self.PB_d, key_mask=self.DMASK, batch=B,
-                       heads=H5, lq=Ld, lk=Ld, dh=DKV, scale=1.0, drop=dec_site(i, 0))
-            self._linear(f, self.O_d[i], p + "o_w", TD, out32=self.HM_d[i], bias=False, res32=self.HS_d[i],
-                         drop=dec_site(i, 1))
-            kp = []
-            self._call(f, "vqa_xattn1_fwd", ops.addr(self.VALL16, i * D), NL * D, self.CTX_d[i], D, B, Ld, H5, DKV,
-                       self._dptr(dec_site(i, 2), kp), extra=kp + [self.VALL16, self.RNG])
-            self._linear(f, self.CTX_d[i], p + "xo_w", TD, out32=self.HX_d[i], bias=False, res32=self.HM_d[i],
-                         drop=dec_site(i, 3))
-            self._call(f, "vqa_rmsnorm_fwd", self.HX_d[i], self.p32[p + "ln2"], None, self.N2_d[i], self.R2_d[i],
-                       TD, D, 1e-6, None)
-            self._linear(f, self.N2_d[i], p + "wi", TD, out16=self.FF_d[i], bias=False, relu=True,
-                         drop=dec_site(i, 4))
-            self._linear(f, self.FF_d[i], p + "wo", TD, out32=self.HS_d[i + 1], bias=False, res32=self.HX_d[i],
-                         drop=dec_site(i, 5))
-        kp = []
-        self._call(f, "vqa_rmsnorm_fwd", self.HS_d[-1], self.p32["dec.final_ln"], self.DEC32, self.DEC16, self.RF_d,
-                   TD, D, 1e-6, self._dptr(SITE_DEC_FINAL, kp), extra=kp + [self.RNG])
+        self.dec.plan_forward(self, f, cross=self._cross_forward)
         # the answer token (last position of the decoder mask), classifier, log_softmax, NLL
         self._call(f, "vqa_last_index", self.DMASK, B, Ld, self.LASTIDX)
         self._call(f, "vqa_gather_rows", self.DEC32, D, self.LASTIDX, 0, 0, self.ANS32, D, B, D, 4)
         self._call(f, "vqa_head_fwd", self.ANS32, self.DUMMY_PW, self.DUMMY_PB, self.p32["cls_w"], self.p32["cls_b"],
                    self.TGT, self.ATT, self.POOLED, self.LOGP, self.NLL, self.LOSS, B, 1, D, self.A)
 
-    def _t5_forward(self, f, pre, ids, mask, T, Lq, HS, N0, QKV, PT, O, HM, N1, FF, R0, R1, PB, bucket):
-        B = self.B
+    def _cross_forward(self, f, st, i):
+        """The decoder's cross sub-layer (T5Stack.plan_forward's `cross`): hx = hm + drop(xo(ctx)),
+        ctx = drop(1) * v, v = layer i's columns of the one value projection VALL16."""
         kp = []
-        self._call(f, "vqa_embedding_fwd", ids, self.p32["embed"], HS[0], T, D, S.T5_VOCAB, self._dptr(SITE_EMBED, kp),
-                   extra=kp + [self.RNG])
-        self._call(f, "vqa_t5_relbias_fwd", self.p32[pre + ".relbias"], bucket, PB, H5, Lq, Lq)
-        for i in range(NL):
-            p = f"{pre}.{i}."
-            self._call(f, "vqa_rmsnorm_fwd", HS[i], self.p32[p + "ln0"], None, N0[i], R0[i], T, D, 1e-6, None)
-            self._linear(f, N0[i], p + "qkv_w", T, out16=QKV[i], bias=False)
-            q = QKV[i]
-            self._attn(f, "vqa_attn_fwd", q=q, ldq=3 * D, k=ops.addr(q, D), ldk=3 * D, v=ops.addr(q, 2 * D),
-                       ldv=3 * D, o=O[i], ldo=D, p=PT[i], bias=PB, key_mask=mask, batch=B, heads=H5, lq=Lq, lk=Lq,
-                       dh=DKV, scale=1.0, drop=t5_site(i, 0))
-            self._linear(f, O[i], p + "o_w", T, out32=HM[i], bias=False, res32=HS[i], drop=t5_site(i, 1))
-            self._call(f, "vqa_rmsnorm_fwd", HM[i], self.p32[p + "ln1"], None, N1[i], R1[i], T, D, 1e-6, None)
-            self._linear(f, N1[i], p + "wi", T, out16=FF[i], bias=False, relu=True, drop=t5_site(i, 2))
-            self._linear(f, FF[i], p + "wo", T, out32=HS[i + 1], bias=False, res32=HM[i], drop=t5_site(i, 3))
+        self._call(f, "vqa_xattn1_fwd", ops.addr(self.VALL16, i * D), NL * D, st.CTX[i], D, self.B, self.Ld, H5, DKV,
+                   self._dptr(dec_site(i, 2), kp), extra=kp + [self.VALL16, self.RNG])
+        self._linear(f, st.CTX[i], f"dec.{i}.xo_w", self.TD, out32=st.HX[i], bias=False, res32=st.HM[i],
+                     drop=dec_site(i, 3))
 
     # ------------------------------------------------------------------ backward
     def _plan_backward(self):
         b = self.bwd_calls
-        B, Lq, Ld, T, TD = self.B, self.L, self.Ld, self.T, self.TD
-        ks = self.drop_scale if self.p_drop > 0.0 else 1.0
+        B, Lq, T, TD = self.B, self.L, self.T, self.TD
         z = self.g32["embed"]
         self._call(b, "vqa_embedding_zero_rows", self.IDS_PREV, self.IDS_ALL, T + TD, z, D, S.T5_VOCAB)
         self._call(b, "vqa_head_bwd", self.ANS32, self.ATT, self.POOLED, self.LOGP, self.TGT, self.DUMMY_PW,
@@ -322,60 +271,8 @@ class VitVQAEngine(EngineBase):
         self._call(b, "vqa_zero", self.dDEC32, TD * D * 4)
         self._call(b, "vqa_scatter_rows", self.dANS32, D, self.LASTIDX, 0, 0, self.dDEC32, D, B, D, 4)
         # ---- decoder (reverse): dH32 = gradient of the residual stream, dH16 the FF-branch gradient
-        dH32, dR32 = self.dH32_d, self.dR32
-        kp, ws = [], self._norm_ws(TD)
-        self._call(b, "vqa_rmsnorm_bwd", self.dDEC32, self.HS_d[-1], self.RF_d, self.p32["dec.final_ln"], None,
-                   dH32, self.dH16[0], None, 0.0, ws, TD, D, self._dptr(SITE_DEC_FINAL, kp), None,
-                   self._dptr(dec_site(NL - 1, 5), kp), extra=kp + [self.RNG])
-        self._defer(ws, L.load().vqa_norm_bwd_parts(TD), D, D, self.g32["dec.final_ln"])
-        cur = 0
-        for i in reversed(range(NL)):
-            p = f"dec.{i}."
-            dH16 = self.dH16[cur]
-            # FF sub-layer: h_out = hx + drop(wo(drop(relu(wi(rms(hx))))))
-            self._dx(b, dH16[:TD], p + "wo", TD, out16=self.dF16[:TD], mask16=self.FF_d[i], alpha=ks)
-            self._dw(b, dH16[:TD], self.FF_d[i], p + "wo", TD)
-            self._dx(b, self.dF16[:TD], p + "wi", TD, out32=self.dC32[:TD])
-            self._dw(b, self.dF16[:TD], self.N2_d[i], p + "wi", TD)
-            kp, ws = [], self._norm_ws(TD)
-            self._call(b, "vqa_rmsnorm_bwd", self.dC32, self.HX_d[i], self.R2_d[i], self.p32[p + "ln2"], dH32,
-                       self.dX32, self.dB16, None, 0.0, ws, TD, D, None, None, self._dptr(dec_site(i, 3), kp),
-                       extra=kp + [self.RNG])
-            self._defer(ws, L.load().vqa_norm_bwd_parts(TD), D, D, self.g32[p + "ln2"])
-            # cross sub-layer: hx = hm + drop(xo(ctx)), ctx = drop(1) * v  (q, k, the cross norm: zero grads)
-            self._dx(b, self.dB16[:TD], p + "xo_w", TD, out16=self.dO16[:TD])
-            self._dw(b, self.dB16[:TD], self.CTX_d[i], p + "xo_w", TD)
-            kp = []
-            self._call(b, "vqa_xattn1_bwd", self.dO16, D, None, ops.addr(self.dVALL16, i * D), NL * D, B, Ld, H5, DKV,
-                       self._dptr(dec_site(i, 2), kp), extra=kp + [self.dVALL16, self.RNG])
-            kp, ws = [], self._norm_ws(TD)
-            self._call(b, "vqa_rmsnorm_bwd", self.ZERO32, self.HM_d[i], self.R0_d[i], self.p32[p + "ln1"], self.dX32,
-                       dR32, self.dB16, None, 0.0, ws, TD, D, None, None, self._dptr(dec_site(i, 1), kp),
-                       extra=kp + [self.RNG])
-            self._defer(ws, L.load().vqa_norm_bwd_parts(TD), D, D, self.g32[p + "ln1"])
-            # self-attention sub-layer
-            self._dx(b, self.dB16[:TD], p + "o_w", TD, out16=self.dO16[:TD])
-            self._dw(b, self.dB16[:TD], self.O_d[i], p + "o_w", TD)
-            q, dq = self.QKV_d[i], self.dQKV16
-            self._attn(b, "vqa_attn_bwd", q=q, ldq=3 * D, k=ops.addr(q, D), ldk=3 * D, v=ops.addr(q, 2 * D),
-                       ldv=3 * D, p=self.PT_d[i], bias=self.PB_d, key_mask=self.DMASK, batch=B, heads=H5, lq=Ld,
-                       lk=Ld, dh=DKV, scale=1.0, dout=self.dO16, lddo=D, dq=dq, lddq=3 * D, dk=ops.addr(dq, D),
-                       lddk=3 * D, dv=ops.addr(dq, 2 * D), lddv=3 * D, dbias=self.dSB_d[i], drop=dec_site(i, 0),
-                       keep=(dq,))
-            self._dx(b, dq[:TD], p + "qkv_w", TD, out32=self.dC32[:TD])
-            self._dw(b, dq[:TD], self.N0_d[i], p + "qkv_w", TD)
-            kp = []
-            nxt = self.dH16[1 - cur]
-            d32 = self._dptr(SITE_DEC_EMBED, kp) if i == 0 else None
-            d16 = self._dptr(dec_site(i - 1, 5), kp) if i > 0 else None
-            ws = self._norm_ws(TD)
-            self._call(b, "vqa_rmsnorm_bwd", self.dC32, self.HS_d[i], self.R0_d[i], self.p32[p + "ln0"], dR32, dH32,
-                       nxt if i > 0 else None, None, 0.0, ws, TD, D, None, d32, d16, extra=kp + [self.RNG])
-            self._defer(ws, L.load().vqa_norm_bwd_parts(TD), D, D, self.g32[p + "ln0"])
-            cur = 1 - cur
-        self._call(b, "vqa_batch_sum", self.dSB_d, NL * B, H5 * Ld * Ld, self.dPB_d, 0.0)
-        self._call(b, "vqa_t5_relbias_bwd", self.dPB_d, self.bucket_d, self.g32["dec.relbias"], H5, Ld, Ld,
-                   S.T5_BUCKETS)
+        self.dec.plan_backward(self, b, self._t5_grads(TD, self.dDEC32, self.dH32_d), self._dxdw,
+                               cross=self._cross_backward)
         # ---- the fused token: all layers' value projections, then the fusing layer
         ksf = (1.0 / (1.0 - VM.FUSE_P)) if self.p_drop > 0.0 else 1.0
         self._gemm(b, self.dVALL16, self.p16["dec.xv_w"], B, D, NL * D, lda=NL * D, ldb=D, b_trans=True,
@@ -387,54 +284,30 @@ class VitVQAEngine(EngineBase):
         self._dw(b, self.dPRE16, self.CAT16, "fuse_w", B, bias_from=self.dPRE16)
         # ---- encoder: the CLS rows' gradient, final norm, layers
         self._call(b, "vqa_scatter_rows", self.dCLS32, D, None, Lq, 0, self.dTXT32, D, B, D, 4)
-        self._t5_backward(b, ks)
+        self.enc.plan_backward(self, b, self._t5_grads(T, self.dTXT32, self.dH32_e), self._dxdw)
         self._flush(b)
         self._call(b, "vqa_embedding_bwd", self.IDS_ALL, self.dH32_ALL, self.g32["embed"], T + TD, D, S.T5_VOCAB,
                    self.WS_EMB)
 
-    def _t5_backward(self, b, ks):
-        B, Lq, T = self.B, self.L, self.T
-        dH32, dR32 = self.dH32_e, self.dR32
-        kp, ws = [], self._norm_ws(T)
-        self._call(b, "vqa_rmsnorm_bwd", self.dTXT32, self.HS_e[-1], self.RF_e, self.p32["enc.final_ln"], None,
-                   dH32, self.dH16[0], None, 0.0, ws, T, D, self._dptr(SITE_FINAL, kp), None,
-                   self._dptr(t5_site(NL - 1, 3), kp), extra=kp + [self.RNG])
-        self._defer(ws, L.load().vqa_norm_bwd_parts(T), D, D, self.g32["enc.final_ln"])
-        cur = 0
-        for i in reversed(range(NL)):
-            p = f"enc.{i}."
-            dH16 = self.dH16[cur]
-            self._dx(b, dH16[:T], p + "wo", T, out16=self.dF16[:T], mask16=self.FF_e[i], alpha=ks)
-            self._dw(b, dH16[:T], self.FF_e[i], p + "wo", T)
-            self._dx(b, self.dF16[:T], p + "wi", T, out32=self.dC32[:T])
-            self._dw(b, self.dF16[:T], self.N1_e[i], p + "wi", T)
-            kp, ws = [], self._norm_ws(T)
-            self._call(b, "vqa_rmsnorm_bwd", self.dC32, self.HM_e[i], self.R1_e[i], self.p32[p + "ln1"], dH32, dR32,
-                       self.dB16, None, 0.0, ws, T, D, None, None, self._dptr(t5_site(i, 1), kp),
-                       extra=kp + [self.RNG])
-            self._defer(ws, L.load().vqa_norm_bwd_parts(T), D, D, self.g32[p + "ln1"])
-            self._dx(b, self.dB16[:T], p + "o_w", T, out16=self.dO16[:T])
-            self._dw(b, self.dB16[:T], self.O_e[i], p + "o_w", T)
-            q, dq = self.QKV_e[i], self.dQKV16
-            self._attn(b, "vqa_attn_bwd", q=q, ldq=3 * D, k=ops.addr(q, D), ldk=3 * D, v=ops.addr(q, 2 * D),
-                       ldv=3 * D, p=self.PT_e[i], bias=self.PB_e, key_mask=self.MASK, batch=B, heads=H5, lq=Lq,
-                       lk=Lq, dh=DKV, scale=1.0, dout=self.dO16, lddo=D, dq=dq, lddq=3 * D, dk=ops.addr(dq, D),
-                       lddk=3 * D, dv=ops.addr(dq, 2 * D), lddv=3 * D, dbias=self.dSB_e[i], drop=t5_site(i, 0),
-                       keep=(dq,))
-            self._dx(b, dq[:T], p + "qkv_w", T, out32=self.dC32[:T])
-            self._dw(b, dq[:T], self.N0_e[i], p + "qkv_w", T)
-            kp = []
-            nxt = self.dH16[1 - cur]
-            d32 = self._dptr(SITE_EMBED, kp) if i == 0 else None
-            d16 = self._dptr(t5_site(i - 1, 3), kp) if i > 0 else None
-            ws = self._norm_ws(T)
-            self._call(b, "vqa_rmsnorm_bwd", self.dC32, self.HS_e[i], self.R0_e[i], self.p32[p + "ln0"], dR32, dH32,
-                       nxt if i > 0 else None, None, 0.0, ws, T, D, None, d32, d16, extra=kp + [self.RNG])
-            self._defer(ws, L.load().vqa_norm_bwd_parts(T), D, D, self.g32[p + "ln0"])
-            cur = 1 - cur
-        self._call(b, "vqa_batch_sum", self.dSB_e, NL * B, H5 * Lq * Lq, self.dPB_e, 0.0)
-        self._call(b, "vqa_t5_relbias_bwd", self.dPB_e, self.bucket_e, self.g32["enc.relbias"], H5, Lq, Lq,
-                   S.T5_BUCKETS)
+    def _t5_grads(self, rows, dout, dh32):
+        """T5Grads of a stack of `rows` rows: both stacks run their backward through the one shared
+        scratch (the layers are serial and their weight gradients in line), the FF-branch gradient
+        ping-pongs between the two dH16."""
+        per_layer = lambda buf: [buf[:rows]] * NL                 # noqa: E731
+        return T5Grads([self.dH16[(NL - 1 - i) & 1][:rows] for i in range(NL)], per_layer(self.dF16),
+                       per_layer(self.dB16), per_layer(self.dQKV16), dout, dh32, self.dR32[:rows], self.dC32[:rows],
+                       self.dO16[:rows], self.dX32[:rows])
+
+    def _cross_backward(self, b, st, i, g):
+        """The decoder's cross sub-layer (T5Stack.plan_backward's `cross`): xo, the value columns'
+        gradient; q, k and the cross norm get exactly zero gradients, so its backward runs with
+        dy = 0 and only carries the residual gradient and the self-attention branch's dropout."""
+        self._dxdw(b, g.dHM[i], st.CTX[i], f"dec.{i}.xo_w", self.TD, out16=g.dO16)
+        kp = []
+        self._call(b, "vqa_xattn1_bwd", g.dO16, D, None, ops.addr(self.dVALL16, i * D), NL * D, self.B, self.Ld, H5,
+                   DKV, self._dptr(dec_site(i, 2), kp), extra=kp + [self.dVALL16, self.RNG])
+        st.norm_bwd(self, b, self.ZERO32, st.HM[i], st.R0[i], f"dec.{i}.ln1", g.dHX32, g.dHM32, g.dHM[i],
+                    (None, None, dec_site(i, 1)))
 
     # ------------------------------------------------------------------ optimizer
     def _plan_optimizer(self):

@@ -11,6 +11,26 @@ def _engine(pkg, image):
     return pkg.engine.VQAEngine(sd, vision="resnet50", batch=2, seq_len=16, image_size=image)
 
 
+@pytest.mark.gpu
+def test_t5_dw_group_int_is_its_list(pkg):
+    """A group size is kept as the list of group sizes it stands for, and plans what that list
+    plans; 1 is the paired per-layer form, with one mark per T5 layer."""
+    sd = pkg.synthetic.make_state_dict("resnet50", seed=0)
+
+    def build(g):
+        return pkg.engine.VQAEngine(sd, vision="resnet50", batch=2, seq_len=16, image_size=64, t5_dw_group=g)
+
+    def plan(eng):
+        return [(c.name, c.side) for c in eng.bwd_calls]
+    by_size, by_list = build(4), build((4, 4, 4))
+    assert by_size.t5_dw_groups == [4, 4, 4] == by_list.t5_dw_groups
+    assert plan(by_size) == plan(by_list) and by_size.ready_marks == by_list.ready_marks
+    paired = build(1)
+    assert paired.t5_dw_groups is None
+    ends = {sg.offset + (sg.numel + 63) // 64 * 64 for sg in (paired.lay[f"t5.{i}.ln1"] for i in range(paired.nl))}
+    assert len(ends) == paired.nl and ends <= {end for _, end in paired.ready_marks}
+
+
 def _names(eng):
     return {k: [c.name for c in getattr(eng, k)] for k in ("res_calls", "opt_calls", "tail_calls", "emb_pre")}
 

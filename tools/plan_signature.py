@@ -1,0 +1,156 @@
+"""Canonical, pointer-free signature of the engines' plans: an A/B of two trees whose planned
+call lists must be the same (a refactor of the Python plans).  Engines are only built; no step
+runs.  For every config of the matrix below and every call of fwd_calls / bwd_calls / opt_calls
+(and zero_calls / tail_calls / emb_pre / res_calls where the engine has them) one JSON line
+holds the call's name, its `side` tag, its non-address arguments, the non-pointer fields of its
+descriptors, and every address as [rank of first appearance of the storage that owns it, byte
+offset in that storage] (the owners are the call's `keep`, as ops.uncovered_pointers reads them;
+an address no kept storage owns gets a rank of its own).  A host dropout structure passed by
+address is written out by value, and the job table of vqa_colsum_batched is decoded.
+  python tools/plan_signature.py > plan_new.json               # once per tree, then compare
+  python tools/plan_signature.py --digest-of plan_new.json     # per list: calls and a SHA-256"""
+import argparse
+import ctypes
+import hashlib
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import load_package  # noqa: E402
+
+LISTS = ("fwd_calls", "bwd_calls", "opt_calls", "zero_calls", "tail_calls", "emb_pre", "res_calls")
+MARKS = ("_fsplit", "_bsplit", "ready_marks", "_sq_split", "_t5_layer_start")
+RESNET = (("defaults", {}), ("fuse_norm", dict(fuse_norm=True)),
+          ("dw_group_1", dict(t5_dw_group=1, sga_dw_batch=False)), ("dw_group_4", dict(t5_dw_group=4)),
+          ("dw_group_12", dict(t5_dw_group=12)), ("dw_groups_4431", dict(t5_dw_group=(4, 4, 3, 1))),
+          ("pipeline", dict(pipeline=True)), ("dropout_0", dict(dropout=0.0)), ("fp8", dict(fp8=True)),
+          ("pair_bwd_off", dict(pair_bwd=False)))
+VIT = (("vit_dropout_0.1", dict(dropout=0.1)), ("vit_dropout_0", dict(dropout=0.0)))
+
+
+class Canon:
+    """Addresses of one engine -> [rank, offset]."""
+
+    def __init__(self, pkg):
+        self.ops, self.L = pkg.ops, pkg.lib
+        self.rank = {}
+
+    def _owners(self, call):
+        dev, host = [], []
+
+        def add(o):
+            if isinstance(o, torch.Tensor):
+                st = o.untyped_storage()
+                dev.append((st.data_ptr(), st.data_ptr() + st.nbytes()))
+            elif isinstance(o, ctypes.Structure):
+                host.append((ctypes.addressof(o), o))
+            elif isinstance(o, (tuple, list)):
+                for x in o:
+                    add(x)
+        add(call.keep or ())
+        return dev, host
+
+    def addr(self, p, owners):
+        if not p:
+            return None
+        dev, host = owners
+        for a, o in host:
+            if a == p:
+                return {"host": type(o).__name__, **self.struct(o, owners)}
+        lo = next((a for a, b in dev if a <= p < b), None)
+        key = ("storage", lo) if lo is not None else ("unowned", p)
+        r = self.rank.setdefault(key, len(self.rank))
+        return [r, p - lo] if lo is not None else [r, 0, "unowned"]
+
+    def struct(self, s, owners):
+        ptrs = self.ops._PTR_FIELDS.get(type(s).__name__, ()) + (("rng",) if isinstance(s, self.L.Dropout) else ()) + \
+            (("ws", "out") if isinstance(s, self.L.ColsumJob) else ())
+        out = {}
+        for name, *_ in s._fields_:
+            v = getattr(s, name)
+            if name in ptrs:
+                out[name] = self.addr(v, owners)
+            elif isinstance(v, ctypes.Structure):
+                out[name] = self.struct(v, owners)
+            elif isinstance(v, ctypes.Array):
+                out[name] = list(v)
+            else:
+                out[name] = v
+        return out
+
+    def call(self, c):
+        owners = self._owners(c)
+        ptr_args = {w for w, _ in self.ops._pointers(c)}
+        args = []
+        for i, a in enumerate(c.args):
+            obj = getattr(a, "_obj", None)                      # ctypes.byref(desc)
+            if obj is not None:
+                args.append({type(obj).__name__: self.struct(obj, owners)})
+            elif f"arg{i}" in ptr_args:
+                args.append({"addr": self.addr(a, owners)})
+            else:
+                args.append(a)
+        out = {"name": c.name, "side": bool(getattr(c, "side", False)), "args": args}
+        if c.name == "vqa_colsum_batched":                      # its job table lives in device memory
+            raw = c.keep[-1].cpu().numpy().tobytes()
+            jobs = (self.L.ColsumJob * c.args[1]).from_buffer_copy(raw)
+            out["jobs"] = [self.struct(j, owners) for j in jobs]
+        return out
+
+
+def flat(calls):
+    for c in calls:
+        if hasattr(c, "calls"):                                 # engine_base._Seq
+            yield from flat(c.calls)
+        else:
+            yield c
+
+
+def signature(pkg, eng):
+    cn = Canon(pkg)
+    out = {k: [cn.call(c) for c in flat(getattr(eng, k))] for k in LISTS if getattr(eng, k, None) is not None}
+    out.update({k: getattr(eng, k, None) for k in MARKS})
+    return out
+
+
+def digest(sig):
+    """A signature with every call list replaced by its length and SHA-256 (the matrix in full is
+    several MB)."""
+    return {k: {"calls": len(v), "sha256": hashlib.sha256(json.dumps(v, sort_keys=True).encode()).hexdigest()}
+            if k in LISTS else v for k, v in sig.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--digest-of", default=None, metavar="FILE",
+                    help="print the digest form of a saved signature (no engine is built, no GPU needed)")
+    ap.add_argument("--only", default=None, help="comma-separated config names (default: the whole matrix)")
+    args = ap.parse_args()
+    if args.digest_of:
+        for line in open(args.digest_of):
+            print(json.dumps(digest(json.loads(line)), sort_keys=True))
+        return
+    pkg = load_package()
+    only = set(args.only.split(",")) if args.only else None
+    sd = pkg.synthetic.make_state_dict("resnet50", seed=0)
+    vsd = pkg.vit_model.make_state_dict(seed=0, image=32)
+    for name, kw in RESNET + VIT:
+        if only and name not in only:
+            continue
+        if name.startswith("vit_"):
+            eng = pkg.vit_engine.VitVQAEngine(vsd, batch=2, seq_len=16, dec_len=8, image_size=32, device=args.device,
+                                              **kw)
+        else:
+            eng = pkg.engine.VQAEngine(sd, vision="resnet50", batch=2, seq_len=16, image_size=64, device=args.device,
+                                       **kw)
+        print(json.dumps({"config": name, **signature(pkg, eng)}, sort_keys=True))
+        del eng
+
+
+if __name__ == "__main__":
+    main()
