@@ -25,23 +25,22 @@ Design (MI355X-first, not a translation of eager PyTorch):
     (include/vqa_hip.h "dropout"); the backward regenerates the masks, nothing
     is stored.  dropout=0 gives eval-mode numerics (golden-vector parity).
 
-This module holds what is the ResNet engine's own: the frozen-ResNet plan, the SGA / head
-forward and backward plans (fused norms, fp8, batched weight gradients), the deferred and
-row-split optimizer plan, the stream schedule of the step, graph capture and the evaluation
-graph.  The T5 encoder is planned by t5_stack.T5Stack, the plan the ViT engine's stacks use
-too; what this engine adds to it is its own: activations stacked per layer and one gradient slot
+This module holds what is the ResNet engine's own: the frozen-ResNet plan, the scaler and head
+calls, the fp8 arenas, the deferred and row-split optimizer plan, the stream schedule of the step,
+graph capture and the evaluation graph.  The SGA blocks are planned by sga_stack.SGAStack, the T5
+encoder by t5_stack.T5Stack, the plan the ViT engine's stacks use too; what this engine adds to
+the latter is its own: activations stacked per layer and one gradient slot
 per layer, so that the weight gradients run per group of layers as batched launches on the side
 stream (t5_dw_group, _t5_group_dw; t5_dw_groups is its one form: the list of group sizes, or
 None for paired dX + dW per layer), the ready marks between groups, and opt-in fuse_norm.  The
 arenas, the call builders, the AdamW descriptors and the state-dict / optimizer-state readouts
 are engine_base.EngineBase's, shared with vit_engine.VitVQAEngine; the GEMM tuner is tune.py.
-The C ABI stays at 22: the shared plan issues the calls the three plans issued.
+The C ABI stays at 22: the stacks issue the calls the engines' own plans issued.
 """
 from __future__ import annotations
 
 import ctypes
 import os
-import math
 
 import numpy as np
 import torch
@@ -51,15 +50,10 @@ from . import ops
 from . import synthetic as S
 from .engine_base import (BF16, F32, I64, IGNORE_INDEX, SITE_EMBED, SITE_FINAL, EngineBase, _after,  # noqa: F401
                           _check_attn_path, _h2d, _Seq, batch_rows, load_rows, load_rows_multi, no_gc_capture,
-                          t5_site)
+                          t5_site)       # (_check_attn_path, _h2d and sga_site: re-exported, tests/test_api_cpu.py)
 from .layout import ParamLayout, fold_bn, t5_bucket_map
+from .sga_stack import SGAGrads, SGAStack, sga_site  # noqa: F401
 from .t5_stack import T5Grads, T5Stack
-
-
-def sga_site(block, kind):
-    """kind 0 mhatt1 probs, 1 dropout1, 2 mhatt2 probs, 3 dropout2, 4 MLP inner, 5 dropout3
-    (multi_head_vision_text_attn.py:84, 146, 84, 150, 99, 154)"""
-    return 128 + 8 * block + kind
 
 
 def stem_s2d_weight(wf):
@@ -84,7 +78,7 @@ class VQAEngine(EngineBase):
         # GEMM that writes its input (vqa_gemm_desc.norm) instead of as a launch of its own;
         # same bits.  Opt-in; None reads the environment (VQA_FUSE_NORM=1).
         self.fuse_norm = (os.environ.get("VQA_FUSE_NORM", "0") == "1") if fuse_norm is None else bool(fuse_norm)
-        self.fuse_norm_kept = []          # norms left stand-alone although fuse_norm is on, with the reason
+        self.fuse_norm_kept = []          # norms left stand-alone although fuse_norm is on: none (always empty)
         # pipeline: the frozen ResNet (no trainable input) of the NEXT batch runs on its own
         # stream beside this step's T5 / SGA / backward / optimizer (see train_step)
         self.pipeline = bool(pipeline)
@@ -337,7 +331,7 @@ class VQAEngine(EngineBase):
 
     def _alloc_activations(self):
         D = self.D
-        B, Lq, T, NB, V = self.B, self.L, self.T, self.NB, self.V_TOK
+        B, Lq, T, V = self.B, self.L, self.T, self.V_TOK
         t = self._t
         # inputs
         self.IDS = t((B, Lq), I64, zero=True)
@@ -351,50 +345,23 @@ class VQAEngine(EngineBase):
         self.t5 = T5Stack(self, "t5.", T, Lq, self.nl, self.h5, self.dkv, self.dff, D, self.IDS, self.MASK,
                           self.bucket, t5_site, (2, 3), SITE_EMBED, SITE_FINAL, embed="t5.embed", stacked=True)
         self.TXT32, self.TXT16 = self.t5.OUT32, self.t5.OUT16
-        # SGA blocks; the self-attention halves of all blocks share batched buffers:
-        # q|k|v of block n in columns [n*2304, (n+1)*2304) of QKV1A, merge in/out in [n]
-        self.QKV1A = t((T, NB * 3 * D), BF16)
-        self.O1A, self.S1A = t((NB, T, D), BF16), t((NB, T, D))
-        self.P1A = t((NB, B, self.sga_heads, Lq, Lq))         # their attention probabilities, stacked
-        # inputs of the blocks' q2 / m2 / fc1 / fc2 weight gradients, stacked in backward order
-        # (slot NB-1-n) for the batched dW launches
-        self.X1hS, self.O2S, self.X2hS, self.FFhS = (t((NB, T, D), BF16) for _ in range(4))
-        self.Q2S = t((NB, T, D), BF16)                 # the blocks' cross-attention queries (one batched GEMM)
-        if self.fuse_norm:
-            # the batched merge writes every block's norm1 outputs: one signed stride per output
-            # kind, so X1 is stacked like X1hS (slot NB-1-n), the statistics in block order
-            self.X1S, self.MU1S, self.RS1S = t((NB, T, D)), t((NB, T)), t((NB, T))
-            # arrival counters of the norm-carrying GEMMs (zero-filled, left zero by every launch):
-            # one block for the T5 encoder's chain and one for the SGA blocks'.  Each chain is
-            # serial on its stream; the two never overlap (the fusion segment starts after the
-            # text branch has joined), and neither the vision branch beside the encoder nor the
-            # pipelined ResNet of the next batch has a norm-carrying GEMM
-            self.NORM_WS = [torch.zeros(65536 // 4, dtype=torch.int32, device=self.dev) for _ in range(2)]
-        self.sga = []
-        for n in range(NB):
-            ly = V if n == 0 else T
-            lk = self.fh * self.fh if n == 0 else Lq
-            self.sga.append(dict(
-                ly=ly, lk=lk,
-                P1=self.P1A[n], O1=self.O1A[n], S1=self.S1A[n],
-                X1=self.X1S[NB - 1 - n] if self.fuse_norm else t((T, D)), X1h=self.X1hS[NB - 1 - n],
-                MU1=self.MU1S[n] if self.fuse_norm else t(T), RS1=self.RS1S[n] if self.fuse_norm else t(T),
-                Q2=self.Q2S[NB - 1 - n], KV2=t((ly, 2 * D), BF16), P2=t((B, self.sga_heads, Lq, lk)),
-                O2=self.O2S[NB - 1 - n], S2=t((T, D)), X2=t((T, D)), X2h=self.X2hS[NB - 1 - n], MU2=t(T), RS2=t(T),
-                FFh=self.FFhS[NB - 1 - n], S3=t((T, D)), OUT=t((T, D)), OUTh=t((T, D), BF16), MU3=t(T), RS3=t(T)))
+        # arrival counters of the norm-carrying GEMMs (zero-filled, left zero by every launch): one
+        # block for the T5 encoder's chain and one for the SGA blocks'.  Each chain is serial on
+        # its stream; the two never overlap (the fusion segment starts after the text branch has
+        # joined), and neither the vision branch beside the encoder nor the pipelined ResNet of
+        # the next batch has a norm-carrying GEMM
+        self.NORM_WS = [torch.zeros(65536 // 4, dtype=torch.int32, device=self.dev) for _ in range(2)] \
+            if self.fuse_norm else (None, None)
+        self.sga_stack = SGAStack(self, self.TXT32, self.TXT16, self.VIS16, self.NORM_WS[1])
+        self.sga, self.P1A, self.O1A = self.sga_stack.blocks, self.sga_stack.P1A, self.sga_stack.O1A
         # head
         self.ATT, self.POOLED = t((B, Lq)), t((B, D))
         self.LOGP, self.NLL, self.LOSS = t((B, self.A)), t(B), t(1)
         self.ROWTOT = t(1, zero=True)     # DP: valid rows summed over the ranks (use_global_rows)
         # backward temporaries (reused layer to layer)
-        mx = max(T, V)
         self.dY = [t((T, D)), t((T, D))]
         self.dA32 = t((T, D))
-        self._gbufs = {}
         self.dC32 = t((T, D))
-        self.dTA = [t((T, D)), t((T, D))]              # running text gradient of the SGA norm1s (ping-pong)
-        self.dA1A, self.dO1A = t((NB, T, D), BF16), t((NB, T, D), BF16)
-        self.dQKV1A = t((T, NB * 3 * D), BF16)
         self.dO16 = t((T, D), BF16)
         self.dTXT = t((T, D))
         self.dVIS32, self.dVIS16 = t((V, D)), t((V, D), BF16)
@@ -408,39 +375,12 @@ class VQAEngine(EngineBase):
         self.SQ_PARTS = 1024                              # per sqnorm range (three ranges, §3.7)
         self.WS_SQ = t(3 * self.SQ_PARTS, torch.float64)
 
-    # ------------------------------------------------------------------ call helpers (beside EngineBase's)
-    def _sga_self_keep(self):
-        """The flat-arena views the batched SGA self-attention launches read past: the
-        blocks' q|k|v and merge weights, biases and gradients sit side by side (layout.py)."""
-        names = [f"sga{n}.{w}" for w in ("qkv1_w", "qkv1_b", "m1_w", "m1_b") for n in range(self.NB)]
-        for w in ("qkv1_w", "qkv1_b", "m1_w", "m1_b"):
-            segs = [self.lay[f"sga{n}.{w}"] for n in range(self.NB)]
-            assert all(b.offset == a.offset + a.numel for a, b in zip(segs, segs[1:])), w
-        return tuple(self.p16[k] for k in names if k in self.p16) + tuple(self.p32[k] for k in names) + \
-            tuple(self.g32[k] for k in names)
-
-    def _sga_groups(self):
-        """vqa_attn_desc group fields of the SGA blocks' self-attentions: all NB blocks in one
-        launch (block n: q|k|v columns n*2304 of QKV1A, O1A[n] / dO1A[n], P1A[n], dropout site
-        sga_site(n, 0)), or one block per launch (sga_attn_group=False)."""
-        T, D = self.B * self.L, self.D
-        if not self.sga_attn_group or self.NB == 1:
-            return dict(groups=1)
-        return dict(groups=self.NB, gstride_qkv=3 * D, gstride_o=T * D, gstride_dout=T * D,
-                    gstride_p=self.P1A[0].numel(), gdrop_site_stride=sga_site(1, 0) - sga_site(0, 0))
-
     # ------------------------------------------------------------------ fp8 (config 5)
     FP8_T5 = ("qkv_w", "o_w", "wi", "wo")
     FP8_SGA = ("qkv1_w", "m1_w", "q2_w", "kv2_w", "m2_w", "fc1_w", "fc2_w")
 
     def _is_fp8(self, wname):
         return self.fp8 and wname.rsplit(".", 1)[-1] in (self.FP8_T5 + self.FP8_SGA)
-
-    def _w8(self, wname):
-        """(e4m3 weight view [n, k], its row scales [n]) of segment `wname` in the fp8 arenas."""
-        sg = self.lay[wname]
-        n, k = sg.shape
-        return self.W8[sg.offset:sg.offset + n * k].view(n, k), self.WSC[sg.offset:sg.offset + n]
 
     def _quant_weight(self, lst, wname, rows=None):
         """Row-wise e4m3 copy of weight `wname` (its fp32 master, `rows` rows from its offset:
@@ -460,24 +400,11 @@ class VQAEngine(EngineBase):
         self._call(lst, "vqa_quant_rows_fp8", x16, 1, k, rows, k, x8, k, xs)
         return x8, xs
 
-    def _ln_kw(self, g, b, y32, y16, mean, rstd, ws, **strides):
-        """ops.gemm_desc keywords of an SGA LayerNorm fused behind the GEMM that writes its input."""
-        return dict(norm=L.NORM_LAYER, norm_w=g, norm_b=b, norm_eps=1e-5, norm_y32=y32, norm_y16=y16, norm_mean=mean,
-                    norm_rstd=rstd, workspace=ws, **strides)
-
-    def _gbuf(self, name, shape):
-        """A bf16 backward buffer private to one use (see _plan_backward)."""
-        if name not in self._gbufs:
-            self._gbufs[name] = self._t(shape, BF16)
-        return self._gbufs[name]
-
     # ------------------------------------------------------------------ forward plan
     def _plan_forward(self):
         D = self.D
         f = self.fwd_calls
-        B, Lq, T = self.B, self.L, self.T
-        fuse = self.fuse_norm
-        wt5, wsga = self.NORM_WS if fuse else (None, None)   # arrival counters: T5 chain, SGA chain
+        B, Lq = self.B, self.L
         if self.p_drop > 0.0:                                # fresh dropout masks every step
             self._call(f, "vqa_rng_advance", self.RNG)
         self._fsplit = [len(f)]                              # [pre | vision | text | fusion]
@@ -491,112 +418,14 @@ class VQAEngine(EngineBase):
                    c32=self.VIS32, ldc32=D, c16=self.VIS16, ldc16=D, bias=self.p32["scaler_b"])
         # SGA block 0's key/value projection reads only the vision tokens: it runs here, on the
         # vision branch beside the T5 encoder, instead of on the chain after it
-        self._linear(f, self.VIS16, "sga0.kv2_w", self.sga[0]["ly"], out16=self.sga[0]["KV2"])
+        self.sga_stack.plan_kv0(self, f)
         self.sga_vision_calls = [f[-1]]                    # SGA work outside the fusion segment (bench)
         # T5 encoder (independent of the vision branch until the SGA blocks)
         self._fsplit.append(len(f))
-        self.t5.plan_forward(self, f, fuse=wt5)
+        self.t5.plan_forward(self, f, fuse=self.NORM_WS[0])
         self._t5_layer_start = self.t5.layer_start
         self._fsplit.append(len(f))
-        # SGA blocks: x = text always, y chained
-        y16 = self.VIS16
-        sc = 1.0 / math.sqrt(self.sga_dh)
-        # self-attention halves of all blocks first (they only read the T5 output): one q|k|v
-        # projection with N = 3 * 2304, the blocks' attentions, one batched merge
-        NB, W3 = self.NB, 3 * D
-        if self.fp8:                                          # the blocks' q|k|v weights as one [NB*2304, D] matrix
-            x8, xs = self._quant_act(f, ("sga.qkv1", "x"), self.TXT16, T)
-            w8 = self.W8[self.lay["sga0.qkv1_w"].offset:]
-            self._gemm(f, x8, w8, T, NB * W3, D, lda=D, ldb=D, c16=self.QKV1A, ldc16=NB * W3,
-                       bias=self.p32["sga0.qkv1_b"], fp8=True, scale_a=xs,
-                       scale_b=ops.addr(self.WSC, self.lay["sga0.qkv1_w"].offset),
-                       keep=self._sga_self_keep() + (self.W8, self.WSC))
-        else:
-            self._gemm(f, self.TXT16, self.p16["sga0.qkv1_w"], T, NB * W3, D, lda=D, ldb=D, c16=self.QKV1A,
-                       ldc16=NB * W3, bias=self.p32["sga0.qkv1_b"], keep=self._sga_self_keep())
-        grp = self._sga_groups()
-        for n in range(0, NB, grp["groups"]):
-            s, c0 = self.sga[n], n * W3
-            q = self.QKV1A
-            self._attn(f, "vqa_attn_fwd", q=ops.addr(q, c0), ldq=NB * W3, k=ops.addr(q, c0 + D), ldk=NB * W3,
-                       v=ops.addr(q, c0 + 2 * D), ldv=NB * W3, o=s["O1"], ldo=D, p=s["P1"], batch=B,
-                       heads=self.sga_heads, lq=Lq, lk=Lq, dh=self.sga_dh, scale=sc, drop=sga_site(n, 0),
-                       keep=(q, self.O1A, self.P1A), **grp)
-        m1kw = dict(c32=self.S1A, ldc32=D, bias=self.p32["sga0.m1_b"], res32=self.TXT32, ldres=D, batch=NB,
-                    stride_a=T * D, stride_b=D * D, stride_c32=T * D, stride_res=0, stride_bias=D,
-                    drop_site_stride=sga_site(1, 1) - sga_site(0, 1))
-        fuse1 = fuse
-        if fuse and NB > 1:
-            # the merge is one launch over the blocks: their gamma / beta must sit at one stride
-            gs = [self.lay[f"sga{n}.ln1_g"].offset for n in range(NB)]
-            bs = [self.lay[f"sga{n}.ln1_b"].offset for n in range(NB)]
-            gst = gs[1] - gs[0]
-            fuse1 = all(b_ - a_ == gst for a_, b_ in zip(gs, gs[1:])) and \
-                all(b_ - a_ == gst for a_, b_ in zip(bs, bs[1:])) and gst % 4 == 0
-            if not fuse1:
-                self.fuse_norm_kept.append("sga ln1: gamma / beta of the blocks are not at one constant stride")
-        if fuse1:
-            gst = (self.lay["sga1.ln1_g"].offset - self.lay["sga0.ln1_g"].offset) if NB > 1 else 0
-            m1kw.update(self._ln_kw(self.p32["sga0.ln1_g"], self.p32["sga0.ln1_b"], self.X1S[NB - 1], self.X1hS[NB - 1],
-                                    self.MU1S, self.RS1S, wsga, stride_norm_w=gst, stride_norm_y=-T * D,
-                                    stride_norm_stat=T))
-            m1keep = (self.P32, self.X1S, self.X1hS)
-        else:
-            m1keep = ()
-        if self.fp8:
-            x8, xs = self._quant_act(f, ("sga.m1", "x"), self.O1A.view(NB * T, D), NB * T)
-            o0 = self.lay["sga0.m1_w"].offset
-            self._gemm(f, x8, self.W8[o0:], T, D, D, lda=D, ldb=D, fp8=True, scale_a=xs, stride_scale_a=T,
-                       scale_b=ops.addr(self.WSC, o0), stride_scale_b=D * D,
-                       keep=self._sga_self_keep() + (self.W8, self.WSC) + m1keep, **m1kw)
-        else:
-            self._gemm(f, self.O1A, self.p16["sga0.m1_w"], T, D, D, lda=D, ldb=D,
-                       keep=self._sga_self_keep() + m1keep, **m1kw)
-        self._set_drop(f[-1], sga_site(0, 1))
-        for n in range(NB if not fuse1 else 0):
-            s, p = self.sga[n], f"sga{n}."
-            self._call(f, "vqa_layernorm_fwd", s["S1"], self.p32[p + "ln1_g"], self.p32[p + "ln1_b"], s["X1"],
-                       s["X1h"], s["MU1"], s["RS1"], T, D, 1e-5)
-        # the blocks' cross-attention queries read only their norm1 outputs: one launch
-        # batched over the blocks (stack slot NB-1-n = the blocks' order in the arena)
-        segs = [self.lay[f"sga{n}.q2_w"] for n in reversed(range(NB))]
-        bsegs = [self.lay[f"sga{n}.q2_b"] for n in reversed(range(NB))]
-        wst = segs[1].offset - segs[0].offset if NB > 1 else 0
-        assert all(b_.offset - a_.offset == wst for a_, b_ in zip(segs, segs[1:]))
-        assert all(b_.offset - a_.offset == wst for a_, b_ in zip(bsegs, bsegs[1:]))
-        q2kw = dict(c16=self.Q2S, ldc16=D, bias=self.p32[f"sga{NB - 1}.q2_b"], batch=NB, stride_a=T * D,
-                    stride_b=wst, stride_c16=T * D, stride_bias=wst)
-        if self.fp8:
-            x8, xs = self._quant_act(f, ("sga.q2", "x"), self.X1hS.view(NB * T, D), NB * T)
-            o0 = self.lay[f"sga{NB - 1}.q2_w"].offset
-            self._gemm(f, x8, self.W8[o0:], T, D, D, lda=D, ldb=D, fp8=True, scale_a=xs, stride_scale_a=T,
-                       scale_b=ops.addr(self.WSC, o0), stride_scale_b=wst, keep=(self.P16, self.P32, self.W8, self.WSC),
-                       **q2kw)
-        else:
-            self._gemm(f, self.X1hS, self.p16[f"sga{NB - 1}.q2_w"], T, D, D, lda=D, ldb=D, keep=(self.P16, self.P32),
-                       **q2kw)
-        for n in range(NB):
-            s, p = self.sga[n], f"sga{n}."
-            if n > 0:
-                self._linear(f, y16, p + "kv2_w", s["ly"], out16=s["KV2"])
-            kv = s["KV2"]
-            self._attn(f, "vqa_attn_fwd", q=s["Q2"], ldq=D, k=kv, ldk=2 * D, v=ops.addr(kv, D), ldv=2 * D,
-                       o=s["O2"], ldo=D, p=s["P2"], batch=B, heads=self.sga_heads, lq=Lq, lk=s["lk"], dh=self.sga_dh,
-                       scale=sc, drop=sga_site(n, 2))
-            self._linear(f, s["O2"], p + "m2_w", T, out32=s["S2"], res32=s["X1"], drop=sga_site(n, 3),
-                         norm=self._ln_kw(self.p32[p + "ln2_g"], self.p32[p + "ln2_b"], s["X2"], s["X2h"], s["MU2"],
-                                          s["RS2"], wsga) if fuse else None)
-            if not fuse:
-                self._call(f, "vqa_layernorm_fwd", s["S2"], self.p32[p + "ln2_g"], self.p32[p + "ln2_b"], s["X2"],
-                           s["X2h"], s["MU2"], s["RS2"], T, D, 1e-5)
-            self._linear(f, s["X2h"], p + "fc1_w", T, out16=s["FFh"], relu=True, drop=sga_site(n, 4))
-            self._linear(f, s["FFh"], p + "fc2_w", T, out32=s["S3"], res32=s["X2"], drop=sga_site(n, 5),
-                         norm=self._ln_kw(self.p32[p + "ln3_g"], self.p32[p + "ln3_b"], s["OUT"], s["OUTh"], s["MU3"],
-                                          s["RS3"], wsga) if fuse else None)
-            if not fuse:
-                self._call(f, "vqa_layernorm_fwd", s["S3"], self.p32[p + "ln3_g"], self.p32[p + "ln3_b"], s["OUT"],
-                           s["OUTh"], s["MU3"], s["RS3"], T, D, 1e-5)
-            y16 = s["OUTh"]
+        self.sga_stack.plan_forward(self, f)             # x = text always, y chained
         last = self.sga[-1]["OUT"]
         self._call(f, "vqa_head_fwd", last, self.p32["pool_w"], self.p32["pool_b"], self.p32["cls_w"],
                    self.p32["cls_b"], self.TGT, self.ATT, self.POOLED, self.LOGP, self.NLL, self.LOSS, B, Lq, D, self.A)
@@ -606,7 +435,6 @@ class VQAEngine(EngineBase):
         D = self.D
         b = self.bwd_calls
         B, Lq, T, NB = self.B, self.L, self.T, self.NB
-        nparts = L.load().vqa_norm_bwd_parts(T)
         # the dense embedding gradient only ever gets the touched rows written: re-zero the rows
         # the previous step wrote (IDS_PREV) instead of all 32128 x 768 floats (DP: dp.py swaps in
         # the gathered ids of every rank)
@@ -630,116 +458,8 @@ class VQAEngine(EngineBase):
             sg = self.lay[seg]
             self.ready_marks.append((len(b), sg.offset + (sg.numel + 63) // 64 * 64))
         mark("pool_b")
-        sc = 1.0 / math.sqrt(self.sga_dh)
-        ks = self.drop_scale if self.p_drop > 0.0 else 1.0      # relu-mask dX: kept elements carry 1/(1-p)
-        # the blocks' q2 / m2 / fc1 / fc2 weight gradients (768 x 768, K = 2048 each) are left
-        # out of the sequential block chain and computed after it as one launch per weight
-        # batched over the blocks (the block chain then runs its input gradients alone)
-        self.dA3S, self.dBS, self.dA2S, self.dQS = (self._t((NB, T, D), BF16) for _ in range(4))
-        batched = self.sga_dw_batch
-        dxdw = self._dx_only if batched else self._dxdw
-        for n in reversed(range(NB)):
-            s, p = self.sga[n], f"sga{n}."
-            dy = self.dY[n & 1]
-            y16 = self.VIS16 if n == 0 else self.sga[n - 1]["OUTh"]
-            # every bf16 gradient a weight-gradient GEMM reads gets its own buffer, so the dW
-            # GEMMs can trail the dX chain on another stream without write-after-read hazards
-            g = lambda nm, shape: self._gbuf(f"{p}{nm}", shape)
-            slot = NB - 1 - n
-            dA3, dA2, dB, dQ = self.dA3S[slot], self.dA2S[slot], self.dBS[slot], self.dQS[slot]
-            dKV = g("dKV", (s["ly"], 2 * D))
-            # norm3 + FFN: dA32 = grad of x + dropout3(ffn(x)) (the residual), dA16 = its dropout3 branch;
-            # the fc2 bias gradient (column sums of the branch) is fused into the LayerNorm backward
-            kp = []
-            ws = self._norm_ws()
-            self._call(b, "vqa_layernorm_bwd", dy, s["S3"], s["MU3"], s["RS3"], self.p32[p + "ln3_g"], None,
-                       self.dA32, dA3, None, None, ws, T, D,
-                       self._dptr(sga_site(n, 5), kp), self.g32[p + "fc2_b"], extra=kp + [self.RNG])
-            for j, nm in enumerate(("ln3_g", "ln3_b", "fc2_b")):      # ws = [parts][dgamma | dbeta | dsum]
-                self._defer(ws, nparts, 3 * D, D, self.g32[p + nm], offset=j * D)
-            dxdw(b, dA3, s["FFh"], p + "fc2_w", T, out16=dB, mask16=s["FFh"], alpha=ks)
-            if batched:
-                self._dx(b, dB, p + "fc1_w", T, out32=self.dC32, res32=self.dA32)
-                self._bias_colsum(b, dB, T, p + "fc1_b")
-            else:
-                self._dxdw(b, dB, s["X2h"], p + "fc1_w", T, bias_from=dB, out32=self.dC32, res32=self.dA32)
-            # norm2 + cross attention (q from x, k/v from y)
-            kp = []
-            ws = self._norm_ws()
-            self._call(b, "vqa_layernorm_bwd", self.dC32, s["S2"], s["MU2"], s["RS2"], self.p32[p + "ln2_g"], None,
-                       self.dA32, dA2, None, None, ws, T, D,
-                       self._dptr(sga_site(n, 3), kp), self.g32[p + "m2_b"], extra=kp + [self.RNG])
-            for j, nm in enumerate(("ln2_g", "ln2_b", "m2_b")):      # ws = [parts][dgamma | dbeta | dsum]
-                self._defer(ws, nparts, 3 * D, D, self.g32[p + nm], offset=j * D)
-            dxdw(b, dA2, s["O2"], p + "m2_w", T, out16=self.dO16)
-            kv = s["KV2"]
-            self._attn(b, "vqa_attn_bwd", q=s["Q2"], ldq=D, k=kv, ldk=2 * D, v=ops.addr(kv, D), ldv=2 * D,
-                       p=s["P2"], batch=B, heads=self.sga_heads, lq=Lq, lk=s["lk"], dh=self.sga_dh, scale=sc,
-                       dout=self.dO16, lddo=D, dq=dQ, lddq=D, dk=dKV, lddk=2 * D,
-                       dv=ops.addr(dKV, D), lddv=2 * D, drop=sga_site(n, 2))
-            if batched:
-                self._dx(b, dQ, p + "q2_w", T, out32=self.dC32, res32=self.dA32)
-                self._bias_colsum(b, dQ, T, p + "q2_b")
-            else:
-                self._dxdw(b, dQ, s["X1h"], p + "q2_w", T, bias_from=dQ, out32=self.dC32, res32=self.dA32)
-            if n == 0:
-                self._dxdw(b, dKV, y16, p + "kv2_w", s["ly"], bias_from=dKV, out32=self.dVIS32, out16=self.dVIS16)
-            else:
-                self._dxdw(b, dKV, y16, p + "kv2_w", s["ly"], bias_from=dKV, out32=self.dY[(n - 1) & 1])
-            # norm1: its residual input is the T5 output, so the text gradient of the blocks
-            # accumulates here (dres = the running sum); the merge branch goes to dA1A[n]
-            kp = []
-            ws = self._norm_ws()
-            self._call(b, "vqa_layernorm_bwd", self.dC32, s["S1"], s["MU1"], s["RS1"], self.p32[p + "ln1_g"],
-                       None if n == NB - 1 else self.dTA[(n + 1) & 1], self.dTA[n & 1], self.dA1A[n], None, None,
-                       ws, T, D, self._dptr(sga_site(n, 1), kp), self.g32[p + "m1_b"], extra=kp + [self.RNG])
-            for j, nm in enumerate(("ln1_g", "ln1_b", "m1_b")):      # ws = [parts][dgamma | dbeta | dsum]
-                self._defer(ws, nparts, 3 * D, D, self.g32[p + nm], offset=j * D)
-            if not batched:
-                mark(f"sga{n}.ln3_b")
-        if batched:
-            for w, dys, xs in (("fc2_w", self.dA3S, self.FFhS), ("fc1_w", self.dBS, self.X2hS),
-                               ("m2_w", self.dA2S, self.O2S), ("q2_w", self.dQS, self.X1hS)):
-                segs = [self.lay[f"sga{n}.{w}"] for n in reversed(range(NB))]
-                lstride = segs[1].offset - segs[0].offset if NB > 1 else 0
-                assert all(b_.offset - a_.offset == lstride for a_, b_ in zip(segs, segs[1:])), w
-                self._gemm(b, dys, xs, D, D, T, lda=D, ldb=D, a_trans=True, b_trans=True,
-                           c32=self.g32[f"sga{NB - 1}.{w}"], ldc32=D, batch=NB, stride_a=T * D, stride_b=T * D,
-                           stride_c32=lstride, keep=(self.G32,))
-                b[-1].side = True
-        # the blocks' self-attention halves, batched: merge dX / dW (batch NB), the
-        # attentions, then ONE q|k|v dX GEMM over K = NB * 2304 (it also sums the blocks'
-        # text gradients, plus the norm1 residual sum as res32) paired with ONE q|k|v dW GEMM
-        W3 = 3 * D
-        keep = self._sga_self_keep()
-        self._gemm(b, self.dA1A, self.p16["sga0.m1_w"], T, D, D, lda=D, ldb=D, b_trans=True, c16=self.dO1A,
-                   ldc16=D, batch=NB, stride_a=T * D, stride_b=D * D, stride_c16=T * D, keep=keep)
-        self._gemm(b, self.dA1A, self.O1A, D, D, T, lda=D, ldb=D, a_trans=True, b_trans=True,
-                   c32=self.g32["sga0.m1_w"], ldc32=D, batch=NB, stride_a=T * D, stride_b=T * D,
-                   stride_c32=D * D, keep=keep)
-        b[-1].side = True
-        dq = self.dQKV1A
-        grp = self._sga_groups()
-        for n in reversed(range(0, NB, grp["groups"])):
-            s, c0 = self.sga[n], n * W3
-            q = self.QKV1A
-            self._attn(b, "vqa_attn_bwd", q=ops.addr(q, c0), ldq=NB * W3, k=ops.addr(q, c0 + D), ldk=NB * W3,
-                       v=ops.addr(q, c0 + 2 * D), ldv=NB * W3, p=s["P1"], batch=B, heads=self.sga_heads, lq=Lq, lk=Lq,
-                       dh=self.sga_dh, scale=sc, dout=self.dO1A[n], lddo=D, dq=ops.addr(dq, c0), lddq=NB * W3,
-                       dk=ops.addr(dq, c0 + D), lddk=NB * W3, dv=ops.addr(dq, c0 + 2 * D), lddv=NB * W3,
-                       drop=sga_site(n, 0), keep=(q, dq, self.P1A, self.dO1A), **grp)
-        tmp = []
-        self._gemm(tmp, dq, self.p16["sga0.qkv1_w"], T, D, NB * W3, lda=NB * W3, ldb=D, b_trans=True,
-                   c32=self.dTXT, ldc32=D, res32=self.dTA[0], ldres=D, keep=keep)
-        self._gemm(tmp, dq, self.TXT16, NB * W3, D, T, lda=NB * W3, ldb=D, a_trans=True, b_trans=True,
-                   c32=self.g32["sga0.qkv1_w"], ldc32=D, keep=keep)
-        tmp[1].side = True                         # not paired: the K = NB * 2304 dX wants split-K
-        b.extend(tmp)
-        lib = L.load()
-        ws = self._t(lib.vqa_colsum_workspace_floats(T, NB * W3))
-        self._call(b, "vqa_colsum", dq, 1, T, NB * W3, NB * W3, None, 0.0, ws)
-        self._defer(ws, lib.vqa_colsum_parts(T), NB * W3, NB * W3, self.g32["sga0.qkv1_b"])
-        self._jobs[-1] = self._jobs[-1][:-1] + (self._jobs[-1][-1] + keep,)
+        self.sga_stack.plan_backward(self, b, SGAGrads(self.dY, self.dA32, self.dC32, self.dO16, self.dTXT,
+                                                       self.dVIS32, self.dVIS16), mark)
         mark(f"sga{NB - 1}.m1_b")
         # ConvTranspose2d scaler weight/bias gradient (vision branch: independent of the T5
         # backward below; its own colsum workspace).  The flipped-conv weight column t*C + c
@@ -790,18 +510,11 @@ class VQAEngine(EngineBase):
     def _t5_group_dw(self, lst, i_hi, i_lo):
         """Weight gradients of T5 layers i_hi >= .. >= i_lo: per weight one launch batched over
         the layers (stack slot 11 - i, consecutive gradient segments at a constant stride)."""
-        nl, T, st = self.nl, self.T, self.t5
-        cnt, s0 = i_hi - i_lo + 1, nl - 1 - i_hi
+        st = self.t5
         for w, dys, xs in (("wo", self.dH16S, st.FFS), ("wi", self.dFS, st.N1S), ("o_w", self.dHMS, st.OS),
                            ("qkv_w", self.dQKVS, st.N0S)):
-            nout, kin = self.g32[f"t5.{i_hi}.{w}"].shape
-            segs = [self.lay[f"t5.{i}.{w}"] for i in range(i_hi, i_lo - 1, -1)]
-            lstride = segs[1].offset - segs[0].offset if cnt > 1 else 0
-            assert all(b.offset - a.offset == lstride for a, b in zip(segs, segs[1:])), w
-            self._gemm(lst, ops.addr(dys, s0 * T * nout), ops.addr(xs, s0 * T * kin), nout, kin, T, lda=nout,
-                       ldb=kin, a_trans=True, b_trans=True, c32=self.g32[f"t5.{i_hi}.{w}"], ldc32=kin, batch=cnt,
-                       stride_a=T * nout, stride_b=T * kin, stride_c32=lstride, keep=(dys, xs, self.G32))
-            lst[-1].side = True
+            self._dw_batched(lst, dys, xs, [f"t5.{i}.{w}" for i in range(i_hi, i_lo - 1, -1)], self.T,
+                             slot=self.nl - 1 - i_hi)
 
     # ------------------------------------------------------------------ optimizer plan
     def _plan_optimizer(self):
@@ -1210,7 +923,7 @@ class VQAEngine(EngineBase):
         (6.66 vs 6.78-6.84 ms per step).  dp.DataParallelStep keeps this placement across its
         stage graphs (dp.plan_stages: a segment's side-tagged calls forked beside the next
         chain segment, its gradient bucket all-reduced once that stage has ended).  Every
-        bf16 gradient a side-tagged call reads has its own buffer (_gbuf), so no later chain
+        bf16 gradient a side-tagged call reads has its own buffer, so no later chain
         call overwrites it (tests: test_dw_stream_matches_single_stream_bitwise)."""
         if not self.dw_stream:
             self._run(calls)

@@ -1,14 +1,16 @@
 """EngineBase: what the two training engines (engine.VQAEngine, vit_engine.VitVQAEngine)
 share -- the flat fp32 parameter / gradient / AdamW arenas with their bf16 shadow, the
 builders of prepared library calls (every tensor a call bakes an address of is recorded in
-its `keep`), the AdamW descriptors (the full arena and any sub-range of it), the eager
-forward / backward / optimizer entry points, and the readouts in reference layout
+its `keep`; _wgemm is the one place a weight GEMM gets bf16 or e4m3 operands, _dw_batched the one
+launch over consecutive weight-gradient segments), the AdamW descriptors (the full arena and any
+sub-range of it), the eager forward / backward / optimizer entry points, and the readouts in reference layout
 (state_dict, optimizer state, parameter views).  An engine adds its own plan:
 `_plan_forward` / `_plan_backward` / `_plan_optimizer`, `load_batch`, `train_step`, `capture`.
 The forward-only evaluation graph (eval_plan ... eval_result) is shared too; an engine supplies
 the calls of its evaluation step (`_run_eval_streams`) and says whether it may evaluate
 (`_eval_setup`).  The builders are also what t5_stack.T5Stack, the one plan of a T5 layer stack
-(the ResNet model's encoder, the ViT model's encoder and decoder), appends its calls through.
+(the ResNet model's encoder, the ViT model's encoder and decoder), and sga_stack.SGAStack, the one
+plan of the ResNet model's SGA blocks, append their calls through.
 """
 from __future__ import annotations
 
@@ -280,26 +282,39 @@ class EngineBase:
         p = np.float32(self.p_drop)
         return float(np.float32(1.0) / (np.float32(1.0) - p))
 
-    def _linear(self, lst, x16, wname, m, out32=None, out16=None, bias=True, relu=False, res32=None, drop=None,
-                norm=None):
-        """norm: vqa_gemm_desc norm fields (ops.gemm_desc keywords) of a row norm fused behind
-        this GEMM (fuse_norm), or None."""
-        nkw = dict(norm or {})
-        nkeep = tuple(nkw.pop("keep", ()))
-        if self.fp8 and self._is_fp8(wname):               # e4m3 operands (VQAEngine's fp8 arenas)
-            x8, xs = self._quant_act(lst, (wname, "x"), x16, m)
-            w8, ws = self._w8(wname)
-            n, k = w8.shape
-            self._gemm(lst, x8, w8, m, n, k, lda=k, ldb=k, c32=out32, ldc32=n, c16=out16, ldc16=n,
-                       bias=self.p32[wname[:-1] + "b"] if bias else None, relu=relu, res32=res32, ldres=n, fp8=True,
-                       scale_a=xs, scale_b=ws, keep=(self.W8, self.WSC) + nkeep, **nkw)
-        else:
-            w = self.p16[wname]
-            n, k = w.shape
-            self._gemm(lst, x16, w, m, n, k, lda=k, ldb=k, c32=out32, ldc32=n, c16=out16, ldc16=n,
-                       bias=self.p32[wname[:-1] + "b"] if bias else None, relu=relu, res32=res32, ldres=n, keep=nkeep,
-                       **nkw)
+    def _wgemm(self, lst, x16, wname, m, n=None, batch=None, drop=None, keep=(), **kw):
+        """y = x W^T with weight segment `wname` as one vqa_gemm, on bf16 operands or, for the
+        weights of _is_fp8, on e4m3 ones: the one place that choice is made (the activation's
+        row-wise e4m3 copy, the weight's, both scale vectors, their strides and the keeps).
+        n: the output columns where side-by-side segments form one matrix (default: the segment's
+        rows).  batch: one launch over x16 [batch, m, k] and `batch` segments from `wname` on, at
+        stride kw["stride_b"] (ParamLayout.stride).  kw: the other ops.gemm_desc keywords -- outputs,
+        bias, residual, their strides, a fused norm; drop: the dropout site of the output."""
+        nn, k = self.p16[wname].shape
+        if batch is not None:
+            kw.update(batch=batch, stride_a=m * k)
+        a, b = x16, self.p16[wname]
+        if self.fp8 and self._is_fp8(wname):
+            off = self.lay[wname].offset
+            a, xs = self._quant_act(lst, (wname, "x"), x16, m * (batch or 1))
+            b = self.W8[off:]
+            kw.update(fp8=True, scale_a=xs, scale_b=ops.addr(self.WSC, off))
+            if batch is not None:
+                kw.update(stride_scale_a=m, stride_scale_b=kw.get("stride_b", 0))
+            keep = tuple(keep) + (self.W8, self.WSC)
+        self._gemm(lst, a, b, m, nn if n is None else n, k, lda=k, ldb=k, keep=keep, **kw)
         self._set_drop(lst[-1], drop)
+
+    def _linear_kw(self, x16, wname, m, out32=None, out16=None, bias=True, relu=False, res32=None, drop=None,
+                   norm=None):
+        """_wgemm keywords of a Linear over one weight.  norm: vqa_gemm_desc norm fields
+        (ops.gemm_desc keywords) of a row norm fused behind this GEMM (fuse_norm), or None."""
+        n = self.p16[wname].shape[0]
+        return dict(norm or {}, x16=x16, wname=wname, m=m, c32=out32, ldc32=n, c16=out16, ldc16=n,
+                    bias=self.p32[wname[:-1] + "b"] if bias else None, relu=relu, res32=res32, ldres=n, drop=drop)
+
+    def _linear(self, lst, *args, **kw):
+        self._wgemm(lst, **self._linear_kw(*args, **kw))
 
     def _dx(self, lst, dy16, wname, m, out32=None, out16=None, res32=None, mask16=None, beta=0.0, alpha=1.0):
         """dX[m, k] = alpha * dY[m, n] W[n, k]  (+res) (*mask>0) (+beta*out32)"""
@@ -332,9 +347,22 @@ class EngineBase:
                                 desc=(gx.desc, gw.desc))]
         lst.extend(tmp)
 
-    def _dx_only(self, lst, dy16, x16, wname, rows, **dxkw):
-        """_dxdw without the weight gradient (left to a launch batched over layers)."""
+    def _dx_only(self, lst, dy16, x16, wname, rows, bias_from=None, **dxkw):
+        """_dxdw without the weight gradient (left to _dw_batched, a launch batched over layers)."""
         self._dx(lst, dy16, wname, rows, **dxkw)
+        if bias_from is not None:
+            self._bias_colsum(lst, bias_from, rows, wname[:-1] + "b")
+
+    def _dw_batched(self, lst, dys, xs, names, rows, slot=0, stride=None):
+        """The weight gradients of the consecutive segments `names` as ONE launch: dW_j =
+        dys[slot + j]^T xs[slot + j] over `rows` rows, the stacks and the gradient segments at
+        constant strides (stride: the segments', default ParamLayout.stride).  Tagged `side`."""
+        g = self.g32[names[0]]
+        n, k = g.shape
+        self._gemm(lst, ops.addr(dys, slot * rows * n), ops.addr(xs, slot * rows * k), n, k, rows, lda=n, ldb=k,
+                   a_trans=True, b_trans=True, c32=g, ldc32=k, batch=len(names), stride_a=rows * n, stride_b=rows * k,
+                   stride_c32=self.lay.stride(names) if stride is None else stride, keep=(dys, xs, self.G32))
+        lst[-1].side = True
 
     def _bias_colsum(self, lst, dy16, rows, bname):
         """A Linear bias gradient = column sums of its bf16 output gradient: the partial
@@ -345,11 +373,13 @@ class EngineBase:
         self._call(lst, "vqa_colsum", dy16, 1, rows, n, n, None, 0.0, ws)
         self._defer(ws, lib.vqa_colsum_parts(rows), n, n, self.g32[bname])
 
-    def _defer(self, ws, parts, stride, cols, out, beta=0.0, offset=0):
+    def _defer(self, ws, parts, stride, cols, out, beta=0.0, offset=0, keep=()):
         """Queue the final reduction out = beta*out + sum_p ws[offset + p*stride + c] (a norm
         weight/bias or Linear bias gradient whose per-block partial rows a backward kernel
-        wrote); _flush() finishes every queued one in a single vqa_colsum_batched launch."""
-        self._jobs.append((ops.addr(ws) + 4 * offset, ops.addr(out), stride, parts, cols, beta, (ws, out)))
+        wrote); _flush() finishes every queued one in a single vqa_colsum_batched launch.
+        keep: what the job reads or writes beyond `ws` and `out`."""
+        self._jobs.append((ops.addr(ws) + 4 * offset, ops.addr(out), stride, parts, cols, beta,
+                           (ws, out) + tuple(keep)))
 
     def _flush(self, lst):
         if not self._jobs:

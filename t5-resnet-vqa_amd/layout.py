@@ -126,6 +126,15 @@ class ParamLayout:
     def __getitem__(self, name) -> Segment:
         return self.segments[name]
 
+    def stride(self, names):
+        """Elements between the starts of consecutive segments `names` (0 for one name): what a
+        launch batched over them steps by.  Raises unless it is one constant."""
+        offs = [self.segments[n].offset for n in names]
+        steps = {b - a for a, b in zip(offs, offs[1:])}
+        if len(steps) > 1:
+            raise ValueError(f"segments {list(names)} are not at one constant stride: {sorted(steps)}")
+        return steps.pop() if steps else 0
+
     # ------------------------------------------------------------------ conversions
     def pack(self, sd) -> np.ndarray:
         """reference state_dict (numpy/torch values) -> flat fp32 arena (kernel layout)."""

@@ -53,3 +53,27 @@ def test_plan_ignores_retired_switches_and_stem_follows_the_image_size(pkg, monk
     eng = _engine(pkg, 80)
     assert [c.name for c in eng.res_calls[:3]] == ["vqa_image_to_s2d16", "vqa_gemm", "vqa_maxpool3x3s2_nhwc"]
     assert tuple(eng.IMG8.shape) == (2, 41, 41, 16)
+
+
+PLANS = {"defaults": {}, "fuse_norm": dict(fuse_norm=True), "fp8": dict(fp8=True),
+         "fp8_fuse_norm": dict(fp8=True, fuse_norm=True), "paired_dw": dict(t5_dw_group=1, sga_dw_batch=False),
+         "sga_attn_group_off": dict(sga_attn_group=False), "blocks_1": dict(num_blocks=1),
+         "blocks_2": dict(num_blocks=2)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(PLANS))
+def test_planned_calls_keep_their_buffers_and_fp8_sites(pkg, name):
+    """Every forward / backward call of every plan variant owns (through `keep`) each address it
+    passes, and with fp8 exactly the weight GEMMs meant to run on e4m3 operands do: the T5 q|k|v,
+    o, wi, wo per layer, the three batched SGA GEMMs (q|k|v, merge, q2), and kv2, m2, fc1, fc2 per
+    block."""
+    kw = PLANS[name]
+    nb = kw.get("num_blocks", 3)
+    sd = pkg.synthetic.make_state_dict("resnet50", seed=0, num_attention_blocks=nb)
+    eng = pkg.engine.VQAEngine(sd, vision="resnet50", batch=2, seq_len=16, image_size=64, **kw)
+    assert eng.NB == nb == len(eng.sga)
+    for c in eng.fwd_calls + eng.bwd_calls:
+        assert not pkg.ops.uncovered_pointers(c), (c.name, pkg.ops.uncovered_pointers(c))
+    fp8 = [c for c in eng.fwd_calls if c.name == "vqa_gemm" and c.desc.fp8]
+    assert len(fp8) == ((4 * eng.nl + 3 + 4 * nb) if kw.get("fp8") else 0)

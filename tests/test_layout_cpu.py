@@ -101,3 +101,34 @@ def test_stem_space_to_depth_equals_7x7_stride2(pkg):
         y = F.conv2d(z, w2.permute(0, 3, 1, 2), padding=1)
         ref = F.conv2d(img, w.float().double(), stride=2, padding=3)
         torch.testing.assert_close(y, ref, rtol=1e-12, atol=1e-12)
+
+
+SGA_RUNS = ("q2_w", "q2_b", "m2_w", "fc1_w", "fc2_w", "ln1_g", "ln1_b", "qkv1_w", "qkv1_b", "m1_w", "m1_b")
+T5_RUNS = ("wo", "wi", "o_w", "qkv_w")
+
+
+@pytest.mark.parametrize("lm", ["t5-base", "t5-large"])
+@pytest.mark.parametrize("blocks", [1, 2, 3, 6])
+def test_stride_of_the_batched_launches_runs(pkg, blocks, lm):
+    """ParamLayout.stride: the blocks' / layers' segments that one batched launch steps over sit
+    at one constant stride, a multiple of 4 elements (16-byte vector loads of gamma / beta); the
+    self-attention halves' q|k|v and merge segments are adjacent (one matrix); a run that is not
+    uniform raises."""
+    lay = pkg.layout.ParamLayout("resnet50", 170, blocks, lm)
+    for w in SGA_RUNS:
+        names = [f"sga{n}.{w}" for n in range(blocks)]
+        st = lay.stride(names)
+        assert st % 4 == 0 and lay.stride(names[::-1]) == -st
+        assert [lay[b].offset - lay[a].offset for a, b in zip(names, names[1:])] == [st] * (blocks - 1)
+        assert (st == 0) == (blocks == 1)
+        if w.startswith(("qkv1", "m1")) and blocks > 1:
+            assert st == lay[names[0]].numel
+    nl = lay.dims.t5_layers
+    for w in T5_RUNS:
+        names = [f"t5.{i}.{w}" for i in reversed(range(nl))]
+        st = lay.stride(names)
+        assert st > 0 and st % 4 == 0
+        assert [lay[b].offset - lay[a].offset for a, b in zip(names, names[1:])] == [st] * (nl - 1)
+        assert lay.stride(names[3:5]) == st and lay.stride(names[:1]) == 0
+    with pytest.raises(ValueError):
+        lay.stride(["cls_w", "pool_w", "sga0.q2_w"])

@@ -2,9 +2,10 @@
 builds or two trees that must give the same bits: run once per side, compare the printed lines).
 Builds the bench engine (B = 64, 224², pipelined, tuned, graphed, dropout 0.1), runs 3 steps and
 prints the losses and a SHA-256 of the fp32 parameters, AdamW moments, bf16 shadow and log-probs.
-  python tools/lib_bitwise.py [--fuse-norm | --dp-groups | --model vit]
+  python tools/lib_bitwise.py [--fuse-norm | --dp-groups | --config5 | --model vit]
 --fuse-norm: the engine with fuse_norm; --dp-groups: with dp.dp_t5_dw_groups' weight-gradient
-groups; --model vit: VitVQAEngine at B = 4, seq_len 16, dec_len 8, 224², dropout 0.1, untuned,
+groups; --config5: bench.py --config5's engine (t5-large, six blocks, e4m3 forward weight GEMMs)
+at 224²; --model vit: VitVQAEngine at B = 4, seq_len 16, dec_len 8, 224², dropout 0.1, untuned,
 graphed, over vit_model.make_batch batches."""
 import argparse
 import hashlib
@@ -23,6 +24,7 @@ from __graft_entry__ import load_package  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--fuse-norm", action="store_true")
 ap.add_argument("--dp-groups", action="store_true")
+ap.add_argument("--config5", action="store_true")
 ap.add_argument("--model", choices=("resnet", "vit"), default="resnet")
 opt = ap.parse_args()
 if opt.fuse_norm:
@@ -43,13 +45,13 @@ if opt.model == "vit":
         eng.load_batch(pool[i])
         eng.train_step()
 else:
-    args = types.SimpleNamespace(batch=64, seq_len=32, image_size=224, blocks=3, no_pipeline=False,
-                                 dp_groups=opt.dp_groups, config5=False,
+    args = types.SimpleNamespace(batch=64, seq_len=32, image_size=224, blocks=6 if opt.config5 else 3,
+                                 no_pipeline=False, dp_groups=opt.dp_groups, config5=opt.config5,
                                  tune_table=os.path.join(ROOT, "t5-resnet-vqa_amd", "tuning", "gemm_gfx950.json"),
                                  tune_save=None, no_graph=False, shard_optimizer=False, dp_res_split=None,
                                  res_cumask=None)
     pool = [on_dev(pkg.synthetic.make_batch(64, 32, 224, seed=1 + i)) for i in range(4)]
-    eng, _, step = bench.make_step(args, pkg, dev, pool, False, 0, "t5-base")
+    eng, _, step = bench.make_step(args, pkg, dev, pool, False, 0, "t5-large" if opt.config5 else "t5-base")
 losses = []
 for i in range(3):
     step(i)

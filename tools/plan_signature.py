@@ -1,7 +1,8 @@
 """Canonical, pointer-free signature of the engines' plans: an A/B of two trees whose planned
 call lists must be the same (a refactor of the Python plans).  Engines are only built; no step
 runs.  For every config of the matrix below and every call of fwd_calls / bwd_calls / opt_calls
-(and zero_calls / tail_calls / emb_pre / res_calls where the engine has them) one JSON line
+(and zero_calls / tail_calls / tail_calls_unfused / emb_pre / res_calls / quant_all and the calls of
+adam_segs where the engine has them) one JSON line
 holds the call's name, its `side` tag, its non-address arguments, the non-pointer fields of its
 descriptors, and every address as [rank of first appearance of the storage that owns it, byte
 offset in that storage] (the owners are the call's `keep`, as ops.uncovered_pointers reads them;
@@ -22,13 +23,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from __graft_entry__ import load_package  # noqa: E402
 
-LISTS = ("fwd_calls", "bwd_calls", "opt_calls", "zero_calls", "tail_calls", "emb_pre", "res_calls")
+LISTS = ("fwd_calls", "bwd_calls", "opt_calls", "zero_calls", "tail_calls", "emb_pre", "res_calls", "quant_all",
+         "adam_segs", "tail_calls_unfused")
 MARKS = ("_fsplit", "_bsplit", "ready_marks", "_sq_split", "_t5_layer_start")
 RESNET = (("defaults", {}), ("fuse_norm", dict(fuse_norm=True)),
           ("dw_group_1", dict(t5_dw_group=1, sga_dw_batch=False)), ("dw_group_4", dict(t5_dw_group=4)),
           ("dw_group_12", dict(t5_dw_group=12)), ("dw_groups_4431", dict(t5_dw_group=(4, 4, 3, 1))),
           ("pipeline", dict(pipeline=True)), ("dropout_0", dict(dropout=0.0)), ("fp8", dict(fp8=True)),
-          ("pair_bwd_off", dict(pair_bwd=False)))
+          ("pair_bwd_off", dict(pair_bwd=False)), ("sga_attn_group_off", dict(sga_attn_group=False)),
+          ("blocks_1", dict(num_blocks=1)), ("blocks_1_fuse_norm", dict(num_blocks=1, fuse_norm=True)),
+          ("fp8_fuse_norm", dict(fp8=True, fuse_norm=True)), ("defer_optimizer_off", dict(defer_optimizer=False)),
+          ("large_6_fp8", dict(language_model="t5-large", num_blocks=6, fp8=True)))
 VIT = (("vit_dropout_0.1", dict(dropout=0.1)), ("vit_dropout_0", dict(dropout=0.0)))
 
 
@@ -104,6 +109,8 @@ class Canon:
 
 def flat(calls):
     for c in calls:
+        if isinstance(c, tuple):                                # an adam_segs entry: (range name, call)
+            c = c[1]
         if hasattr(c, "calls"):                                 # engine_base._Seq
             yield from flat(c.calls)
         else:
@@ -137,7 +144,7 @@ def main():
         return
     pkg = load_package()
     only = set(args.only.split(",")) if args.only else None
-    sd = pkg.synthetic.make_state_dict("resnet50", seed=0)
+    sds = {}                                                    # state dicts by (blocks, language model)
     vsd = pkg.vit_model.make_state_dict(seed=0, image=32)
     for name, kw in RESNET + VIT:
         if only and name not in only:
@@ -146,8 +153,12 @@ def main():
             eng = pkg.vit_engine.VitVQAEngine(vsd, batch=2, seq_len=16, dec_len=8, image_size=32, device=args.device,
                                               **kw)
         else:
-            eng = pkg.engine.VQAEngine(sd, vision="resnet50", batch=2, seq_len=16, image_size=64, device=args.device,
-                                       **kw)
+            key = (kw.get("num_blocks", 3), kw.get("language_model", "t5-base"))
+            if key not in sds:
+                sds[key] = pkg.synthetic.make_state_dict("resnet50", seed=0, num_attention_blocks=key[0],
+                                                         language_model=key[1])
+            eng = pkg.engine.VQAEngine(sds[key], vision="resnet50", batch=2, seq_len=16, image_size=64,
+                                       device=args.device, **kw)
         print(json.dumps({"config": name, **signature(pkg, eng)}, sort_keys=True))
         del eng
 
