@@ -270,6 +270,22 @@ int vqa_attn_probs(const vqa_attn_desc* d, hipStream_t stream);
 int vqa_attn_headmean(const vqa_attn_desc* d, float* aug, long long ld_aug, hipStream_t stream);
 int vqa_rollout_cls(const float* aug, int layers, int batch, int n, long long ld_aug, long long layer_stride,
                     float* mask, float* mask_unit, hipStream_t stream);
+/* The CNN models' heat map (CNN_vqa_heatmap.py:131-137) over an NHWC bf16 feature map x [batch,
+ * positions, channels] (the layer4 map of ResnetVQAModel, the FPN 'pool' level of FasterRcnnVQAModel):
+ *   cam[b, p] = mean_c x[b, p, c] (fp32), heat[b, p] = (cam - min_p cam) / (max_p cam - min_p cam).
+ * mean (may be NULL) gets cam, heat the normalised map; a constant map (positions == 1 included)
+ * gives 0 / 0 = NaN, as the reference's expression does.  channels % 8 == 0, 1 <= positions <= 1024,
+ * x 16-byte aligned.  counter: batch * VQA_CAM_COUNTER_STRIDE zero-initialised words (one
+ * 256-byte line per image), left zero by every launch -- an image's positions are split over
+ * workgroups and the one that arrives last normalises.  The summation order is fixed and there
+ * are no float atomics: the same bits every run. */
+#define VQA_CAM_COUNTER_STRIDE 64
+int vqa_channel_cam(const void* x, int batch, int positions, int channels, float* mean, float* heat,
+                    unsigned* counter, hipStream_t stream);
+/* Nearest-neighbour 2x upsample of an NHWC bf16 map (the FPN's top-down path, F.interpolate(...,
+ * mode="nearest") at an exact factor 2): dst[b, y, x, :] = src[b, y / 2, x / 2, :], dst [batch, 2h,
+ * 2w, channels].  channels % 8 == 0, both 16-byte aligned. */
+int vqa_upsample2x_nhwc(const void* src, void* dst, int batch, int h, int w, int channels, hipStream_t stream);
 
 /* ----------------------------------------------------------------- norms ---
  * Rows of width d (d % 256 == 0, d <= 1024), fp32 in, fp32 and/or bf16 out.

@@ -15,7 +15,8 @@ Layout:
   tune.py        the GEMM tuner (tile config + split-K per prepared GEMM)
   layout.py      the flat arena <-> reference state_dict mapping
   ops.py         prepared C-ABI calls (descriptors built once, replayed)
-  model.py       mirror of the reference module API (ResnetVQAModel)
+  model.py       mirror of the reference module API (ResnetVQAModel,
+                 FasterRcnnVQAModel, VitVQAModel)
   trainer.py     train_one_step / epoch loops of the reference trainer
   dp.py          the data-parallel (RCCL over xGMI) step
   data.py        the collate's image path on the GPU (resize + ToTensor)

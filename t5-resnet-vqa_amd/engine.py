@@ -35,7 +35,7 @@ stream (t5_dw_group, _t5_group_dw; t5_dw_groups is its one form: the list of gro
 None for paired dX + dW per layer), the ready marks between groups, and opt-in fuse_norm.  The
 arenas, the call builders, the AdamW descriptors and the state-dict / optimizer-state readouts
 are engine_base.EngineBase's, shared with vit_engine.VitVQAEngine; the GEMM tuner is tune.py.
-The C ABI stays at 22: the stacks issue the calls the engines' own plans issued.
+The stacks issue the calls the engines' own plans issued.
 """
 from __future__ import annotations
 
@@ -90,6 +90,8 @@ class VQAEngine(EngineBase):
         self._rstream_plain = None        # ... and the engine's own, put back by reset_res_cumask
         self.EMB_MARK = None              # row marks of the split embedding update (_plan_optimizer)
         self.SQ_CNT = None                # arrival counter of vqa_grad_sqnorm_final (_plan_optimizer)
+        self.heat_call = None             # vqa_channel_cam over F4 (_plan_heat)
+        self._fpn_plan = None             # faster-rcnn: the pyramid's call list and maps (fpn_maps)
         self.vision, self.B, self.L, self.H = vision, batch, seq_len, image_size
         assert image_size % 2 == 0, "the space-to-depth stem needs an even image size"
         self.NB, self.A = num_blocks, answer_spaces
@@ -146,7 +148,7 @@ class VQAEngine(EngineBase):
         self.T = batch * seq_len
         self.rows = batch                 # real rows of the loaded batch (a short last batch is padded)
         self.lay = ParamLayout(vision, answer_spaces, num_blocks, dm)
-        sd = {k: np.asarray(v) for k, v in state_dict.items()}
+        sd = S.upgrade_fpn_keys({k: np.asarray(v) for k, v in state_dict.items()})
         self._frozen = {k: v for k, v in sd.items() if k not in set(self.lay.trainable_keys)}
         with torch.cuda.device(self.dev):
             self._alloc_params(sd)
@@ -185,12 +187,33 @@ class VQAEngine(EngineBase):
             self._xq = {}
 
     def _plan_resnet(self, sd):
-        """Frozen torchvision ResNet (eval BN folded) as a list of implicit-GEMM convs."""
-        B, H = self.B, self.H
-        vm = "vision_model."
+        """Frozen torchvision ResNet (eval BN folded) as a list of implicit-GEMM convs; for
+        faster-rcnn the FPN backbone's body and, behind it, the two convs of its 'pool' level."""
         self.res_calls = []
         self._res_keep = []
-        convs = []                                   # (name_conv, name_bn, stride, pad, relu, role)
+        self._res_body(sd, self.res_calls)
+
+    def _res_body(self, sd, calls, pyramid=False):
+        """The vision branch's calls appended to `calls`.  pyramid=False: the plan of the training
+        and evaluation steps, which allocates IMG, the ping-pong buffers and F4 / F4N.
+        pyramid=True (faster-rcnn, fpn_maps): a second list over the same IMG with buffers of its
+        own -- the body with dedicated outputs for C2..C4, then the whole FPN; returns the five
+        levels' NHWC bf16 maps."""
+        B, H = self.B, self.H
+        frcnn = self.vision == S.FASTER_RCNN
+        assert frcnn or not pyramid
+        self._conv_calls = calls                     # where _conv appends
+        vm = S.vision_prefix(self.vision)
+        fpn = "vision_model.fpn."
+
+        def up(w, b):
+            w16 = torch.from_numpy(np.ascontiguousarray(w)).to(self.dev).to(BF16)
+            b32 = torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(self.dev)
+            self._res_keep += [w16, b32]
+            return w16, b32
+
+        def fpn_w(name):                             # a biased conv without a norm: [Cout, kh, kw, Cin]
+            return up(sd[fpn + name + ".0.weight"].astype(np.float32).transpose(0, 2, 3, 1), sd[fpn + name + ".0.bias"])
 
         def conv_w(cname, bname, s2d=False):
             w = sd[vm + cname + ".weight"].astype(np.float32)
@@ -205,8 +228,9 @@ class VQAEngine(EngineBase):
             return w16, b32
 
         # geometry walk to size the ping-pong buffers
-        layers = S.RESNET_LAYERS[self.vision]
-        bottleneck = self.vision == "resnet50"
+        arch = S.body_arch(self.vision)
+        layers = S.RESNET_LAYERS[arch]
+        bottleneck = arch == "resnet50"
         h1 = (H + 2 * 3 - 7) // 2 + 1
         h2 = (h1 + 2 - 3) // 2 + 1
         plan = []                                     # (kind, args)
@@ -222,19 +246,28 @@ class VQAEngine(EngineBase):
                     maxel = max(maxel, B * ho * ho * (planes + cin))
                 plan.append((li, bi, stride, hh, ho, cin, planes, out))
                 hh, cin = ho, out
-        self.fh, self.fc = hh, cin                    # layer4 spatial size / channels
-        self.V_TOK = B * hh * hh
-        self.IMG = self._t((B, 3, H, H))
-        hz = H // 2 + 1                               # space-to-depth stem image (vqa_image_to_s2d16)
+        h5, c5 = hh, cin                              # layer4 spatial size / channels
+        if frcnn:
+            # the vision map is the FPN's 'pool' level: max_pool2d(P5, 1, 2) = P5[:, :, ::2, ::2]
+            # = the 3x3 pad-1 conv of the lateral map at stride 2 (DESIGN: "Faster-RCNN backbone")
+            hh, cin = (h5 - 1) // 2 + 1, S.FPN_CHANNELS
         bufs = [self._t(maxel, BF16) for _ in range(5)]
-        self.res_bufs = bufs
-        self.F4 = self._t((B, hh, hh, cin), BF16)
-        # pipelined: the ResNet writes the next batch's layer4 map here; each step first
-        # moves it into F4 (read by the ConvTranspose2d forward and weight gradient)
-        self.F4N = self._t((B, hh, hh, cin), BF16) if self.pipeline else self.F4
-        # F4 <- F4N as a library kernel (a torch copy_ would put a runtime memcpy node in the graph)
-        self.copy_f4 = ops.Call("vqa_copy", self.F4.data_ptr(), self.F4N.data_ptr(), self.F4.numel() * 2,
-                                keep=(self.F4, self.F4N))
+        hz = H // 2 + 1                               # space-to-depth stem image (vqa_image_to_s2d16)
+        if pyramid:
+            out_map = self._t((B, hh, hh, cin), BF16)
+        else:
+            self.fh, self.fc = hh, cin                # the vision map's spatial size / channels
+            self.V_TOK = B * hh * hh
+            self.IMG = self._t((B, 3, H, H))
+            self.res_bufs = bufs
+            self.F4 = self._t((B, hh, hh, cin), BF16)
+            # pipelined: the ResNet writes the next batch's vision map here; each step first
+            # moves it into F4 (read by the ConvTranspose2d forward and weight gradient)
+            self.F4N = self._t((B, hh, hh, cin), BF16) if self.pipeline else self.F4
+            # F4 <- F4N as a library kernel (a torch copy_ would put a runtime memcpy node in the graph)
+            self.copy_f4 = ops.Call("vqa_copy", self.F4.data_ptr(), self.F4N.data_ptr(), self.F4.numel() * 2,
+                                    keep=(self.F4, self.F4N))
+            out_map = self.F4N
 
         # stem: conv7x7/2 + BN + ReLU, then maxpool 3x3/2
         # (as a 4x4 stride-1 conv over the space-to-depth image: K 256 instead of 7*7*8 = 392)
@@ -244,27 +277,41 @@ class VQAEngine(EngineBase):
         # even, hz == h1 + 1 and h2 == h1 // 2 hold too)
         fused_img = H % 32 == 0
         # the space-to-depth image only exists for the form that reads it (B x hz x hz x 16 bf16)
-        self.IMG8 = None if fused_img else self._t((B, hz, hz, 16), BF16)
+        if not pyramid:
+            self.IMG8 = None if fused_img else self._t((B, hz, hz, 16), BF16)
         if fused_img:
             # space-to-depth + stem + maxpool in one pass (csrc/stem.hip): patches staged from the
             # fp32 image, only the pooled map written; bit-identical to the three-kernel form below
-            self.res_calls.append(ops.Call("vqa_stem_pool_img", self.IMG.data_ptr(), w16.data_ptr(), b32.data_ptr(),
-                                           bufs[1].data_ptr(), B, H, keep=(self.IMG, w16, b32, bufs[1])))
+            calls.append(ops.Call("vqa_stem_pool_img", self.IMG.data_ptr(), w16.data_ptr(), b32.data_ptr(),
+                                  bufs[1].data_ptr(), B, H, keep=(self.IMG, w16, b32, bufs[1])))
         else:
-            self.res_calls.append(ops.Call("vqa_image_to_s2d16", self.IMG.data_ptr(), self.IMG8.data_ptr(), B, H, H,
-                                           keep=(self.IMG, self.IMG8)))
-            self._gemm(self.res_calls, self.IMG8, w16, B * h1 * h1, 64, 256, lda=256, ldb=256, ga=g,
+            calls.append(ops.Call("vqa_image_to_s2d16", self.IMG.data_ptr(), self.IMG8.data_ptr(), B, H, H,
+                                  keep=(self.IMG, self.IMG8)))
+            self._gemm(calls, self.IMG8, w16, B * h1 * h1, 64, 256, lda=256, ldb=256, ga=g,
                        c16=bufs[0], ldc16=64, bias=b32, relu=True)
-            self.res_calls.append(ops.Call("vqa_maxpool3x3s2_nhwc", bufs[0].data_ptr(), bufs[1].data_ptr(), B, h1,
-                                           h1, 64, h2, h2, keep=(bufs[0], bufs[1])))
+            calls.append(ops.Call("vqa_maxpool3x3s2_nhwc", bufs[0].data_ptr(), bufs[1].data_ptr(), B, h1,
+                                  h1, 64, h2, h2, keep=(bufs[0], bufs[1])))
         x = bufs[1]
         free = [bufs[0], bufs[2], bufs[3], bufs[4]]
         nblocks_total = len(plan)
+        own = []                                      # outputs with a buffer of their own: never recycled
+        levels = []                                   # pyramid: (C2..C5 map, its size, its channels)
         for idx, (li, bi, stride, hi, ho, ci, planes, out) in enumerate(plan):
             p = f"layer{li + 1}.{bi}."
-            t1, t2, ds, y = free[0], free[1], free[2], free[3]
-            if idx == nblocks_total - 1:
-                y = self.F4N
+            pool = list(free)
+            t1, t2, ds, y = pool[0], pool[1], pool[2], pool[3]
+            end_of_layer = bi == layers[li] - 1
+            if idx == nblocks_total - 1 and not frcnn:
+                y = out_map
+                own.append(y)
+            elif pyramid and end_of_layer and li < 3:
+                y = self._t((B, ho, ho, out), BF16)
+                own.append(y)
+            if pyramid and end_of_layer:
+                levels.append((y, ho, out))
+
+            def advance():                            # y becomes x; x and the unused buffers are free again
+                return [b_ for b_ in [x] + pool if b_ is not y and not any(b_ is o for o in own)], y
             if bottleneck and (vm + p + "downsample.0.weight") in sd:
                 # conv3 and the 1x1 downsample as ONE GEMM over the concatenated K (r05):
                 # [conv2 out | x subsampled] . [W3 | Wd]^T + (b3 + bd), ReLU -- conv2 writes the
@@ -275,19 +322,17 @@ class VQAEngine(EngineBase):
                 self._conv(x, (B, hi, hi, ci), w, b, 1, 0, t1, relu=True)
                 w, b = conv_w(p + "conv2", p + "bn2")
                 self._conv(t1, (B, hi, hi, planes), w, b, stride, 1, ds, relu=True, ldc16=kc)
-                self.res_calls.append(ops.Call("vqa_subsample_nhwc", x.data_ptr(), B, hi, hi, ci, stride,
-                                               ops.addr(ds, planes), kc, keep=(x, ds)))
+                calls.append(ops.Call("vqa_subsample_nhwc", x.data_ptr(), B, hi, hi, ci, stride,
+                                      ops.addr(ds, planes), kc, keep=(x, ds)))
                 w3, b3 = conv_w(p + "conv3", p + "bn3")
                 wd, bd = conv_w(p + "downsample.0", p + "downsample.1")
                 wcat = torch.cat([w3.reshape(out, planes), wd.reshape(out, ci)], dim=1).contiguous()
                 bcat = b3 + bd
                 self._res_keep += [wcat, bcat]
                 assert B * ho * ho * kc <= ds.numel(), "fused downsample: the [conv2 | x] rows exceed the buffer"
-                self._gemm(self.res_calls, ds, wcat, B * ho * ho, out, kc, lda=kc, ldb=kc, c16=y, ldc16=out,
+                self._gemm(calls, ds, wcat, B * ho * ho, out, kc, lda=kc, ldb=kc, c16=y, ldc16=out,
                            bias=bcat, relu=True)
-                if y is not self.F4N:
-                    free = [x, t1, t2, ds]
-                    x = y
+                free, x = advance()
                 continue
             if bottleneck:
                 w, b = conv_w(p + "conv1", p + "bn1")
@@ -309,9 +354,36 @@ class VQAEngine(EngineBase):
             k3 = 1 if bottleneck else 3
             self._conv(last_in, (B, last_h, last_h, last_c), w3, b3, 1, 1 if k3 == 3 else 0, y, relu=True,
                        res16=res)
-            if y is not self.F4N:
-                free = [x, t1, t2, ds]
-                x = y
+            free, x = advance()
+        if not frcnn:
+            return None
+        # FPN (torchvision FeaturePyramidNetwork.forward): x is C5.  last = inner3(C5); its 'pool'
+        # level, read by the model, is layer3's 3x3 conv taken at stride 2
+        fc_ = S.FPN_CHANNELS
+        lat = free[0] if not pyramid else self._t((B, h5, h5, fc_), BF16)
+        w, b = fpn_w("inner_blocks.3")
+        self._conv(x, (B, h5, h5, c5), w, b, 1, 0, lat, relu=False)
+        w3, b3 = fpn_w("layer_blocks.3")
+        self._conv(lat, (B, h5, h5, fc_), w3, b3, 2, 1, out_map, relu=False)
+        if not pyramid:
+            return None
+        maps = {"pool": out_map, "3": self._t((B, h5, h5, fc_), BF16)}
+        self._conv(lat, (B, h5, h5, fc_), w3, b3, 1, 1, maps["3"], relu=False)
+        last, hl = lat, h5
+        for i in (2, 1, 0):
+            # last = inner_i(C_{i+2}) + nearest-2x(last): the upsampled map is the lateral GEMM's
+            # bf16 residual, so the sum is taken in fp32 and rounded once
+            c, hc, cc = levels[i]
+            assert hc == 2 * hl, "the FPN's top-down path is planned for exact 2x upsamples (image_size % 32 == 0)"
+            ups, nxt = self._t((B, hc, hc, fc_), BF16), self._t((B, hc, hc, fc_), BF16)
+            self._call(calls, "vqa_upsample2x_nhwc", last, ups, B, hl, hl, fc_)
+            w, b = fpn_w(f"inner_blocks.{i}")
+            self._conv(c, (B, hc, hc, cc), w, b, 1, 0, nxt, relu=False, res16=ups)
+            w, b = fpn_w(f"layer_blocks.{i}")
+            maps[str(i)] = self._t((B, hc, hc, fc_), BF16)
+            self._conv(nxt, (B, hc, hc, fc_), w, b, 1, 1, maps[str(i)], relu=False)
+            last, hl = nxt, hc
+        return maps
 
     def _conv(self, x, shape, w16, b32, stride, pad, out, relu, res16=None, ldc16=None):
         n, h, w, c = shape
@@ -326,7 +398,7 @@ class VQAEngine(EngineBase):
         if patch:
             w16 = w16.reshape(cout, 9, c // 64, 64).permute(0, 2, 1, 3).contiguous().reshape(cout, kh, kw, c)
             self._res_keep.append(w16)
-        self._gemm(self.res_calls, x, w16, n * oh * oh, cout, kh * kw * c, lda=kh * kw * c, ldb=kh * kw * c, ga=g,
+        self._gemm(self._conv_calls, x, w16, n * oh * oh, cout, kh * kw * c, lda=kh * kw * c, ldb=kh * kw * c, ga=g,
                    c16=out, ldc16=ldc16 or cout, bias=b32, relu=relu, res16=res16, ldres=cout, a_patch=patch)
 
     def _alloc_activations(self):
@@ -1103,6 +1175,10 @@ class VQAEngine(EngineBase):
                              "build the engine with pipeline=False to evaluate")
         super()._eval_setup(rollout)
 
+    def _eval_heat_setup(self, heatmap):
+        if heatmap:
+            self._plan_heat()
+
     def _run_eval_streams(self):
         """The evaluation step's calls: the forward without its rng advance -- the vision and
         text branches forked over the current stream and `_side`, interleaved as in the training
@@ -1115,6 +1191,8 @@ class VQAEngine(EngineBase):
         self._forward_branches(main, side, f[p0:p1], f[p1:p2])
         self._run(f[p2:])
         self.eval_call(L.stream_handle(main))
+        if self.eval_heatmap:                              # F4 is final since the branches joined
+            self.heat_call(L.stream_handle(main))
 
     # ------------------------------------------------------------------ readouts (tests / API)
     def _model_specs(self):
@@ -1140,3 +1218,53 @@ class VQAEngine(EngineBase):
         """The frozen ResNet's layer4 map of the current batch as NCHW fp32 (the kernels keep
         it NHWC bf16): the `features` generate_answers returns (resnet_vqa_model.py:186-203)."""
         return self.F4[:self.rows].permute(0, 3, 1, 2).float()
+
+    def pool_features(self):
+        """faster-rcnn: the FPN's 'pool' level of the current batch as NCHW fp32 [rows, 256, ph, ph]
+        (the map the model's scaler reads; faster_rcnn_vqa_model.py:102-108)."""
+        if self.vision != S.FASTER_RCNN:
+            raise ValueError(f"pool_features: vision {self.vision!r} has no FPN (layer4_features is its map)")
+        return self.F4[:self.rows].permute(0, 3, 1, 2).float()
+
+    def fpn_maps(self):
+        """faster-rcnn: the five FPN levels {'0','1','2','3','pool'} of the loaded images as NCHW
+        fp32, the dict FasterRcnnVQAModel.generate_answers returns.  A second call list, planned
+        on first use with buffers of its own (the body with C2..C4 kept, then the FPN; the top-down
+        sum is the lateral GEMM's residual epilogue over vqa_upsample2x_nhwc's output) and run
+        eagerly: the training and evaluation plans and their memory are as without it.  'pool' is
+        made by the same two GEMMs as the step's vision map, on the same inputs."""
+        if self.vision != S.FASTER_RCNN:
+            raise ValueError(f"fpn_maps: vision {self.vision!r} has no FPN")
+        if self.H % 32 != 0:
+            raise ValueError(f"fpn_maps: image_size={self.H} is not a multiple of 32: the top-down path is planned "
+                             "for exact 2x nearest upsamples")
+        if self.pipeline:
+            raise ValueError("fpn_maps: a pipelined engine holds the next batch's images; build it with pipeline=False")
+        if self._fpn_plan is None:
+            calls = []
+            with torch.cuda.device(self.dev):
+                maps = self._res_body(self._frozen, calls, pyramid=True)
+            self._fpn_plan = (calls, maps)
+        calls, maps = self._fpn_plan
+        self._run(calls)
+        return {k: maps[k][:self.rows].permute(0, 3, 1, 2).float() for k in ("0", "1", "2", "3", "pool")}
+
+    # ------------------------------------------------------------------ heat map (CNN_vqa_heatmap.py:131-137)
+    def _plan_heat(self):
+        """HEAT / CAM [B, fh, fh] and the vqa_channel_cam call over the vision map F4."""
+        if self.heat_call is None:
+            with torch.cuda.device(self.dev):
+                self.HEAT, self.CAM = self._t((self.B, self.fh, self.fh)), self._t((self.B, self.fh, self.fh))
+                # arrival counters, left at zero by every launch
+                self.HEAT_CNT = self._t(self.B * L.CAM_COUNTER_STRIDE, torch.int32, zero=True)
+            lst = []
+            self._call(lst, "vqa_channel_cam", self.F4, self.B, self.fh * self.fh, self.fc, self.CAM, self.HEAT,
+                       self.HEAT_CNT)
+            self.heat_call = lst[0]
+        return self.heat_call
+
+    def feature_heatmap(self, normalize=True):
+        """The heat map of the current vision map (after a forward): per image the channel mean,
+        min-max normalised (normalize=False: the channel mean itself), [rows, fh, fh] fp32."""
+        self._run([self._plan_heat()])
+        return (self.HEAT if normalize else self.CAM)[:self.rows].clone()

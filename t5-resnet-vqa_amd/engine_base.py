@@ -181,6 +181,7 @@ class EngineBase:
         self.eval_graph = None            # a forward-only evaluation graph (eval_capture)
         self.eval_call = None             # its vqa_eval_rows tail (eval_plan)
         self.eval_rollout = False         # the evaluation step also carries the attention rollout (VitVQAEngine)
+        self.eval_heatmap = False         # ... the vision map's heat map (VQAEngine)
         self._keep_graph = False          # capture(keep_graph=True): the hipGraph_t of each part is kept
         self._scratch = None              # split-K workspace used while autotuning
         self._jobs = []                   # column-sum reductions queued by _defer until _flush
@@ -505,6 +506,13 @@ class EngineBase:
         if rollout:
             raise ValueError("rollout=True: this engine has no attention rollout (VitVQAEngine has)")
 
+    def _eval_heat_setup(self, heatmap):
+        """Hook of eval_plan: raise ValueError if this engine has no feature heat map, else
+        prepare the call its evaluation step issues when `heatmap` is set."""
+        if heatmap:
+            raise ValueError("heatmap=True: this engine has no CNN feature map (VQAEngine has; the ViT model's "
+                             "heat map is rollout=True)")
+
     def _run_eval_streams(self):
         """Hook: issue the evaluation step's calls on the current stream -- the forward without
         its rng advance, then self.eval_call."""
@@ -513,13 +521,15 @@ class EngineBase:
     def _new_graph(self):
         return torch.cuda.CUDAGraph(keep_graph=self._keep_graph)
 
-    def eval_plan(self, topk=5, similarity=None, capacity=None, rollout=False):
+    def eval_plan(self, topk=5, similarity=None, capacity=None, rollout=False, heatmap=False):
         """Allocate the evaluation outputs -- TOPK_IDX / TOPK_LOGP [B, topk], and one int32 buffer
         EVAL_BUF = accumulator block (64 bytes) | prediction log | target log, `capacity` rows
         each -- upload the [A, A] similarity table if one is given, and prepare the
         vqa_eval_rows call over LOGP / TGT / NLL / LOSS.  rollout: the step also computes the
-        attention rollout of its images (VitVQAEngine).  Drops an evaluation graph."""
+        attention rollout of its images (VitVQAEngine); heatmap: the heat map of its vision map, into
+        HEAT [B, fh, fh] (VQAEngine).  Drops an evaluation graph."""
         self._eval_setup(bool(rollout))
+        self._eval_heat_setup(bool(heatmap))
         if not 1 <= int(topk) <= L.EVAL_MAX_K:
             raise ValueError(f"topk={topk}: vqa_eval_rows supports 1..{L.EVAL_MAX_K}")
         capacity = self.EVAL_CAPACITY if capacity is None else int(capacity)
@@ -544,9 +554,10 @@ class EngineBase:
             (() if self.EVAL_SIM is None else (self.EVAL_SIM,))
         self.eval_call = ops.Call("vqa_eval_rows", ctypes.byref(d), keep=keep, desc=d)
         self.eval_k, self.eval_capacity, self.eval_rollout = k, capacity, bool(rollout)
+        self.eval_heatmap = bool(heatmap)
         self.eval_graph = None
 
-    def eval_prepare(self, topk=5, similarity=None, capacity=None, graph=True, rollout=False):
+    def eval_prepare(self, topk=5, similarity=None, capacity=None, graph=True, rollout=False, heatmap=False):
         """Make the evaluation plan (and, with `graph`, its graph) match the arguments, reusing
         what exists: a new table of an engine that already has one is copied into place."""
         from .metrics import check_similarity
@@ -555,20 +566,21 @@ class EngineBase:
             capacity = self.eval_capacity if self.eval_call is not None else self.EVAL_CAPACITY
         cap = int(capacity)
         same = (self.eval_call is not None and self.eval_k == int(topk) and self.eval_capacity == cap
-                and (sim is None) == (self.EVAL_SIM is None) and self.eval_rollout == bool(rollout))
+                and (sim is None) == (self.EVAL_SIM is None) and self.eval_rollout == bool(rollout)
+                and self.eval_heatmap == bool(heatmap))
         if not same:
-            self.eval_plan(topk, sim, cap, rollout)
+            self.eval_plan(topk, sim, cap, rollout, heatmap)
         elif sim is not None:
             _h2d(self.EVAL_SIM, sim)
         if graph and self.eval_graph is None:
             self.eval_capture_graph()
 
-    def eval_capture(self, topk=5, similarity=None, capacity=None, rollout=False):
+    def eval_capture(self, topk=5, similarity=None, capacity=None, rollout=False, heatmap=False):
         """Plan (eval_plan) and capture the evaluation graph.  The warm-up launch outside the
         capture leaves RNG, opt_state and the accumulators as it found them.  The training graph
         is untouched: both live on one engine; configure_optimizer / use_global_rows re-plan
         calls this graph does not hold."""
-        self.eval_plan(topk, similarity, capacity, rollout)
+        self.eval_plan(topk, similarity, capacity, rollout, heatmap)
         self.eval_capture_graph()
 
     def eval_capture_graph(self):

@@ -54,8 +54,7 @@ class ParamLayout:
         self.dims = dm = S.lm_dims(language_model)
         D, A = dm.d_model, answer_spaces
         HI = dm.t5_heads * dm.t5_dkv                 # T5 attention inner width (= D for t5-base/large)
-        self.scaler = "downscale_layer" if vision == "resnet50" else "upscale_layer"
-        self.scaler_cin = 2048 if vision == "resnet50" else 512
+        self.scaler, self.scaler_cin = S.scaler_of(vision)
         segs = []
         add = lambda *a, **k: segs.append(Segment(*a, **k))
         add("cls_w", (A, D), "classification_layer", ["classification_layer.weight"])

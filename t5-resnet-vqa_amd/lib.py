@@ -74,6 +74,7 @@ class CopyJob(ctypes.Structure):
 
 COPY_MAX_JOBS = 8
 SQNORM_FINAL_COUNTER_WORDS = 2112      # vqa_grad_sqnorm_final's zero-initialised counter block
+CAM_COUNTER_STRIDE = 64                # vqa_channel_cam: counter words per image (VQA_CAM_COUNTER_STRIDE)
 
 
 class AttnDesc(ctypes.Structure):
@@ -244,6 +245,8 @@ register("vqa_last_index", P, c_int, c_int, P)
 register("vqa_xattn1_fwd", P, c_ll, P, c_ll, c_int, c_int, c_int, c_int, P)
 register("vqa_xattn1_bwd", P, c_ll, P, P, c_ll, c_int, c_int, c_int, c_int, P)
 register("vqa_rollout_cls", P, c_int, c_int, c_int, c_ll, c_ll, P, P)
+register("vqa_channel_cam", P, c_int, c_int, c_int, P, P, P)
+register("vqa_upsample2x_nhwc", P, P, c_int, c_int, c_int, c_int)
 register("vqa_optim_finalize", P, c_int, c_float, c_float, c_int, c_int, c_float, c_float, P)
 
 

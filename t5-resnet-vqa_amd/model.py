@@ -51,8 +51,9 @@ class ParameterGroup:
 
     def named_parameters(self):
         e = self._model.engine
+        specs = self._model.engine._model_specs()
         for k in self._keys():
-            if k.endswith(("running_mean", "running_var", "num_batches_tracked")):
+            if not S.is_parameter(k, specs[k], self._model.vision_model_name):   # buffers (BN statistics)
                 continue
             v = e.param_view(k) if self.trainable else None
             if v is None:
@@ -86,14 +87,17 @@ class ParameterGroup:
 
 
 class ResnetVQAModel:
+    SUPPORTED = SUPPORTED_VISION
+
     def __init__(self, vision_model_name, language_model_name, answer_spaces, fine_tune_lm_encoder=True,
                  fine_tune_lm_decoder=True, fine_tune_vision=True, num_attention_blocks=3, device="cuda",
                  *, batch_size=64, seq_len=32, image_size=224, state_dict=None, seed=0, dropout=0.1,
                  dropout_seed=0):
         # resnet_vqa_model.py:51-58 builds only resnet18/34/50 and fails later for other names;
         # fail here, with the reason.
-        if vision_model_name not in SUPPORTED_VISION:
-            raise ValueError(f"vision_model_name {vision_model_name!r}: this path supports {SUPPORTED_VISION}")
+        if vision_model_name not in self.SUPPORTED:
+            raise ValueError(f"vision_model_name {vision_model_name!r}: {type(self).__name__} supports "
+                             f"{self.SUPPORTED}")
         # t5-base is the reference's model (resnet_vqa_model.py:60-62); t5-large is BASELINE
         # configs[4]: the encoder of the published t5-large sizes with the SGA blocks, scaler,
         # pooler and classifier built at its width 1024 (the reference hard-codes 768 only in
@@ -116,10 +120,11 @@ class ResnetVQAModel:
         self._build(state_dict)
         self.training = True
         # the sub-module attributes the reference trainer reads (faster_rcnn_vqa_trainer.py:231-263)
-        scaler = "downscale_layer" if vision_model_name == "resnet50" else "upscale_layer"
+        scaler = S.scaler_of(vision_model_name)[0]
         self.vision_model = ParameterGroup(self, "vision_model", trainable=False)
         self.lang_model = ParameterGroup(self, "lang_model")
-        self.downscale_layer = ParameterGroup(self, "downscale_layer", trainable=scaler == "downscale_layer")
+        if vision_model_name != S.FASTER_RCNN:             # FasterRcnnVQAModel has no downscale_layer
+            self.downscale_layer = ParameterGroup(self, "downscale_layer", trainable=scaler == "downscale_layer")
         self.upscale_layer = ParameterGroup(self, "upscale_layer", trainable=scaler == "upscale_layer")
         self.sga_modules = ParameterGroup(self, "sga_modules")
         self.attention_pooler = ParameterGroup(self, "attention_pooler")
@@ -129,6 +134,7 @@ class ResnetVQAModel:
     def _build(self, state_dict, **kw):
         sd = {k: (v.detach().cpu().float().numpy() if isinstance(v, torch.Tensor) else np.asarray(v))
               for k, v in state_dict.items()}
+        sd = S.upgrade_fpn_keys(sd)                        # older torchvision's FPN keys (no `.0`)
         missing = [k for k in S.model_specs(self.vision_model_name, self.answer_spaces, self.num_attention_blocks,
                                             self.language_model_name) if k not in sd]
         if missing:
@@ -199,14 +205,18 @@ class ResnetVQAModel:
         hold the map in bf16, so the features carry bf16 rounding)."""
         log_probs, loss = self.forward(question_input_ids, decoder_question_input_ids, question_attention_masks,
                                        decoder_question_attention_masks, annotation_ids, image_tensors)
-        return log_probs, loss, {"features": self.engine.layer4_features()}
+        return log_probs, loss, self._feature_maps()
+
+    def _feature_maps(self):
+        return {"features": self.engine.layer4_features()}
 
     @staticmethod
     def convert_logits_to_predictions(lm_logits):
         """faster_rcnn_vqa_trainer.py:484-488: argmax of exp(log-probs) over the answers."""
         return torch.argmax(torch.exp(lm_logits), dim=1)
 
-    def predict(self, question_input_ids, question_attention_masks, image_tensors, annotation_ids=None, topk=5):
+    def predict(self, question_input_ids, question_attention_masks, image_tensors, annotation_ids=None, topk=5,
+                heatmap=False):
         """The `topk` most probable answers of every row, most probable first (equal
         log-probs by ascending answer index, so column 0 is the argmax the reference takes,
         faster_rcnn_vqa_trainer.py:484-488; its heat-map script's topk(exp(log-probs), 5),
@@ -214,17 +224,33 @@ class ResnetVQAModel:
         real rows; take exp for probabilities.  Runs the evaluation graph (captured on first
         use, engine.eval_capture): eval mode, no dropout draw, a short batch padded as in
         load_batch.  Rows with an annotation id also add to the engine's evaluation
-        accumulators (engine.eval_result)."""
+        accumulators (engine.eval_result).  heatmap=True: the graph also carries the heat map of
+        the vision map (CNN_vqa_heatmap.py:131-137: per image the channel mean, min-max normalised;
+        vqa_channel_cam) and a third item is returned, heat [n, fh, fh] fp32 (a constant map, e.g.
+        a single position, gives 0 / 0 = NaN as the script's expression does; cv2.resize and the
+        colour map stay with the caller)."""
         self.load_batch(question_input_ids, question_attention_masks, image_tensors, annotation_ids)
         e = self.engine
         if e.eval_call is None:
-            e.eval_plan(topk)
-        elif e.eval_k != int(topk):                        # another k: re-plan, keeping table and capacity
-            e.eval_plan(topk, e.EVAL_SIM, e.eval_capacity)
+            e.eval_plan(topk, heatmap=heatmap)
+        elif e.eval_k != int(topk) or e.eval_heatmap != bool(heatmap):   # re-plan, keeping table and capacity
+            e.eval_plan(topk, e.EVAL_SIM, e.eval_capacity, heatmap=heatmap)
         if e.eval_graph is None:
             e.eval_capture_graph()
         e.eval_step()
-        return e.TOPK_IDX[:e.rows].long(), e.TOPK_LOGP[:e.rows].clone()
+        out = (e.TOPK_IDX[:e.rows].long(), e.TOPK_LOGP[:e.rows].clone())
+        return out + (e.HEAT[:e.rows].clone(),) if heatmap else out
+
+    def feature_heatmap(self, question_input_ids, decoder_question_input_ids=None, question_attention_masks=None,
+                        decoder_question_attention_masks=None, annotation_ids=None, image_tensors=None,
+                        answer_input_ids=None, pixel_values=None, answer_attention_masks=None, question_type_ids=None,
+                        normalize=True):
+        """The heat map of the batch's images alone, [n, fh, fh] fp32, by the eager forward and
+        vqa_channel_cam over the vision map -- no evaluation plan needed.  normalize=False: the
+        channel mean before the min-max normalisation."""
+        self.forward(question_input_ids, decoder_question_input_ids, question_attention_masks,
+                     decoder_question_attention_masks, annotation_ids, image_tensors)
+        return self.engine.feature_heatmap(normalize)
 
     # ------------------------------------------------------------------ weights
     def state_dict(self):
@@ -253,6 +279,24 @@ class ResnetVQAModel:
 
     def parameters_count(self):
         return self.engine.lay.num_params
+
+
+class FasterRcnnVQAModel(ResnetVQAModel):
+    """`FasterRcnnVQAModel` (model/faster_rcnn_vqa_model.py) over the same engine: the vision
+    branch is the backbone of torchvision's fasterrcnn_resnet50_fpn -- a ResNet-50 body with
+    FrozenBatchNorm2d and a FeaturePyramidNetwork, no detector -- whose 'pool' level
+    [B, 256, ph, ph] the `upscale_layer` ConvTranspose2d maps to the ph * ph vision tokens.
+    Same constructor keywords, `forward`, `predict`, trainer groups and state-dict keys as the
+    reference's class (no `downscale_layer`; FPN keys are written in torchvision >= 0.14's
+    `.0` form and read in either form); `generate_answers` returns the five FPN maps."""
+    SUPPORTED = (S.FASTER_RCNN,)
+
+    def __init__(self, vision_model_name=S.FASTER_RCNN, language_model_name="t5-base", answer_spaces=170, *args, **kw):
+        super().__init__(vision_model_name, language_model_name, answer_spaces, *args, **kw)
+
+    def _feature_maps(self):
+        """{'0', '1', '2', '3', 'pool'}: NCHW fp32 (bf16-rounded values), image_size % 32 == 0."""
+        return self.engine.fpn_maps()
 
 
 VIT_NAMES = ("google/vit-base-patch16-224-in21k",)

@@ -70,10 +70,37 @@ def lm_dims(language_model="t5-base") -> LMDims:
 
 
 RESNET_LAYERS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3), "resnet50": (3, 4, 6, 3)}
+# FasterRcnnVQAModel's vision branch (model/faster_rcnn_vqa_model.py:51-53): the backbone of
+# torchvision's fasterrcnn_resnet50_fpn -- a ResNet-50 body with FrozenBatchNorm2d plus a
+# FeaturePyramidNetwork; no detector part (RPN, ROI heads, transform) is kept
+FASTER_RCNN = "faster-rcnn"
+FPN_CHANNELS = 256
+FPN_IN = (256, 512, 1024, 2048)                    # C2..C5 = the outputs of layer1..layer4
 
 
-def resnet_specs(arch: str):
-    """torchvision ResNet v1.5 parameter/buffer names and shapes (stride on the 3x3)."""
+def body_arch(vision: str) -> str:
+    """The torchvision ResNet a vision-model name runs (the FPN backbone's body is a ResNet-50)."""
+    return "resnet50" if vision == FASTER_RCNN else vision
+
+
+def vision_prefix(vision: str) -> str:
+    """State-dict prefix of that ResNet's entries."""
+    return "vision_model.body." if vision == FASTER_RCNN else "vision_model."
+
+
+def scaler_of(vision: str):
+    """(name, input channels) of the ConvTranspose2d that maps the vision map to D channels:
+    downscale_layer over layer4's 2048 for resnet50, upscale_layer over 512 for resnet18/34
+    (resnet_vqa_model.py:64-89) and over the FPN's 256 for faster-rcnn (faster_rcnn_vqa_model.py)."""
+    if vision == FASTER_RCNN:
+        return "upscale_layer", FPN_CHANNELS
+    return ("downscale_layer", 2048) if vision == "resnet50" else ("upscale_layer", 512)
+
+
+def resnet_specs(arch: str, frozen_bn: bool = False, head: bool = True):
+    """torchvision ResNet v1.5 parameter/buffer names and shapes (stride on the 3x3).
+    frozen_bn: the norms are FrozenBatchNorm2d (four buffers, no num_batches_tracked);
+    head=False: no fc (the FPN backbone's body)."""
     if arch not in RESNET_LAYERS:
         raise ValueError(f"unsupported vision model {arch!r}")
     bottleneck = arch == "resnet50"
@@ -85,7 +112,8 @@ def resnet_specs(arch: str):
     def bn(name, c):
         for s in ("weight", "bias", "running_mean", "running_var"):
             specs[f"{name}.{s}"] = (c,)
-        specs[f"{name}.num_batches_tracked"] = ()
+        if not frozen_bn:
+            specs[f"{name}.num_batches_tracked"] = ()
 
     conv("conv1", 64, 3, 7)
     bn("bn1", 64)
@@ -106,9 +134,38 @@ def resnet_specs(arch: str):
             if bi == 0 and (stride != 1 or inplanes != out):
                 conv(p + "downsample.0", out, inplanes, 1); bn(p + "downsample.1", out)
             inplanes = out
-    specs["fc.weight"] = (1000, inplanes)
-    specs["fc.bias"] = (1000,)
+    if head:
+        specs["fc.weight"] = (1000, inplanes)
+        specs["fc.bias"] = (1000,)
     return specs
+
+
+def fpn_specs():
+    """torchvision 0.16 FeaturePyramidNetwork over C2..C5: inner_blocks.i a 1x1 conv to 256,
+    layer_blocks.i a 3x3 conv 256 -> 256, each a Conv2dNormActivation with a bias and neither norm
+    nor activation (hence the `.0`), all inner blocks registered before the layer blocks."""
+    specs = OrderedDict()
+    for i, cin in enumerate(FPN_IN):
+        specs[f"inner_blocks.{i}.0.weight"] = (FPN_CHANNELS, cin, 1, 1)
+        specs[f"inner_blocks.{i}.0.bias"] = (FPN_CHANNELS,)
+    for i in range(len(FPN_IN)):
+        specs[f"layer_blocks.{i}.0.weight"] = (FPN_CHANNELS, FPN_CHANNELS, 3, 3)
+        specs[f"layer_blocks.{i}.0.bias"] = (FPN_CHANNELS,)
+    return specs
+
+
+def upgrade_fpn_keys(sd):
+    """A state dict whose FPN entries have the pre-0.14 torchvision form
+    `...fpn.inner_blocks.{i}.{weight,bias}` with the `.0` the Conv2dNormActivation form has
+    (torchvision's FeaturePyramidNetwork._load_from_state_dict does the same); other keys as they are."""
+    out = OrderedDict()
+    for k, v in sd.items():
+        parts = k.split(".")
+        if (k.startswith("vision_model.fpn.") and len(parts) == 5 and parts[2] in ("inner_blocks", "layer_blocks")
+                and parts[4] in ("weight", "bias")):
+            k = ".".join(parts[:4] + ["0", parts[4]])
+        out[k] = v
+    return out
 
 
 def t5_specs(dims=BASE):
@@ -150,18 +207,29 @@ def sga_specs(dims=BASE):
 
 def model_specs(vision: str = "resnet50", answer_spaces: int = 170, num_attention_blocks: int = 3,
                 language_model="t5-base"):
-    """Full `ResnetVQAModel.state_dict()` key -> shape, in module registration order."""
+    """Full `ResnetVQAModel.state_dict()` key -> shape, in module registration order
+    (vision "faster-rcnn": `FasterRcnnVQAModel.state_dict()`, which has no downscale_layer)."""
     d = lm_dims(language_model)
     D = d.d_model
     specs = OrderedDict()
-    for k, s in resnet_specs(vision).items():
-        specs["vision_model." + k] = s
+    if vision == FASTER_RCNN:
+        for k, s in resnet_specs("resnet50", frozen_bn=True, head=False).items():
+            specs["vision_model.body." + k] = s
+        for k, s in fpn_specs().items():
+            specs["vision_model.fpn." + k] = s
+    else:
+        for k, s in resnet_specs(vision).items():
+            specs["vision_model." + k] = s
     for k, s in t5_specs(d).items():
         specs["lang_model." + k] = s
-    specs["upscale_layer.weight"] = (512, D, 3, 3)
-    specs["upscale_layer.bias"] = (D,)
-    specs["downscale_layer.weight"] = (2048, D, 3, 3)
-    specs["downscale_layer.bias"] = (D,)
+    if vision == FASTER_RCNN:
+        specs["upscale_layer.weight"] = (FPN_CHANNELS, D, 3, 3)
+        specs["upscale_layer.bias"] = (D,)
+    else:
+        specs["upscale_layer.weight"] = (512, D, 3, 3)
+        specs["upscale_layer.bias"] = (D,)
+        specs["downscale_layer.weight"] = (2048, D, 3, 3)
+        specs["downscale_layer.bias"] = (D,)
     for n in range(num_attention_blocks):
         for k, s in sga_specs(d).items():
             specs[f"sga_modules.{n}.{k}"] = s
@@ -170,6 +238,16 @@ def model_specs(vision: str = "resnet50", answer_spaces: int = 170, num_attentio
     specs["attention_pooler.attention.0.weight"] = (1, D)
     specs["attention_pooler.attention.0.bias"] = (1,)
     return specs
+
+
+def is_parameter(key: str, shape, vision: str) -> bool:
+    """Whether state-dict entry `key` is an nn.Parameter of the reference module (what
+    `.parameters()` yields and an optimizer indexes) rather than a buffer: BatchNorm statistics
+    are buffers, and so are all four vectors of a FrozenBatchNorm2d -- every 1-D entry of the
+    FPN backbone's body."""
+    if key.endswith(("running_mean", "running_var", "num_batches_tracked")):
+        return False
+    return not (vision == FASTER_RCNN and key.startswith("vision_model.body.") and len(shape) == 1)
 
 
 def _rng(seed: int, key: str) -> np.random.Generator:
@@ -192,6 +270,13 @@ def init_param(key: str, shape, seed: int = 0, vision: str = "resnet50", dims=BA
         return (g.random(n, dtype=np.float32) * np.float32(hi - lo) + np.float32(lo)).reshape(shape)
 
     leaf = key.rsplit(".", 1)[-1]
+    if key.startswith("vision_model.fpn."):
+        # torchvision's FPN init: kaiming_uniform_(a=1) = U(+-sqrt(3 / fan_in)); its zero biases are
+        # replaced by N(0, 0.05) so that a dropped bias shows in every comparison
+        if leaf == "weight":
+            b = np.sqrt(3.0 / (shape[1] * shape[2] * shape[3]))
+            return uniform(-b, b)
+        return normal(0.05)
     if key.startswith("vision_model."):
         if len(shape) == 4:                                   # conv: kaiming-normal fan_out (torchvision)
             return normal(np.sqrt(2.0 / (shape[0] * shape[2] * shape[3])))
@@ -199,7 +284,7 @@ def init_param(key: str, shape, seed: int = 0, vision: str = "resnet50", dims=BA
             b = 1.0 / np.sqrt(shape[-1] if leaf == "weight" else 2048)
             return uniform(-b, b)
         # the BN closing each residual branch gets a small scale so the residual stream stays O(1)
-        last_bn = ".bn3." in key or (vision != "resnet50" and ".bn2." in key)
+        last_bn = ".bn3." in key or (body_arch(vision) != "resnet50" and ".bn2." in key)
         if leaf == "weight":                                  # frozen BN (folded), nontrivial stats
             return uniform(0.15, 0.35) if last_bn else uniform(0.7, 1.3)
         if leaf == "bias":

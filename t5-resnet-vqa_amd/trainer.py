@@ -237,13 +237,14 @@ class VQATrainer:
                      ("fusing_layer", "Fusion Layer", self.group_lr["fusing_layer"]),
                      ("classification_layer", "Classifier Layer", self.group_lr["classification_layer"])]
             return [(label, lr, [k for k in specs if k.split(".", 1)[0] == top]) for top, label, lr in names]
-        scaler = "downscale_layer" if m.vision_model_name == "resnet50" else "upscale_layer"
+        scaler = S.scaler_of(m.vision_model_name)[0]       # faster-rcnn: the UpScaler group (:242-246)
         names = [("vision_model", "Vision Model"), ("lang_model", "Language Model"),
                  (scaler, "DownScaler Layer" if scaler == "downscale_layer" else "UpScaler Layer"),
                  ("sga_modules", "Self-Guided Attention Module"), ("attention_pooler", "Attention Pooler"),
                  ("classification_layer", "Classifier Layer")]
         specs = S.model_specs(m.vision_model_name, m.answer_spaces, m.num_attention_blocks, m.language_model_name)
-        params = [k for k in specs if not k.endswith(("running_mean", "running_var", "num_batches_tracked"))]
+        # (faster-rcnn: 53 + 16 vision parameters -- a FrozenBatchNorm2d has buffers only)
+        params = [k for k, shape in specs.items() if S.is_parameter(k, shape, m.vision_model_name)]
         groups = []
         for top, label in names:
             keys = [k for k in params if k.split(".", 1)[0] == top]

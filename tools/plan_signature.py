@@ -137,6 +137,8 @@ def main():
     ap.add_argument("--digest-of", default=None, metavar="FILE",
                     help="print the digest form of a saved signature (no engine is built, no GPU needed)")
     ap.add_argument("--only", default=None, help="comma-separated config names (default: the whole matrix)")
+    ap.add_argument("--vision", default="resnet50", help="vision model of the VQAEngine configs (resnet50, resnet34, "
+                    "resnet18, faster-rcnn); the config names get it as a prefix unless it is resnet50")
     args = ap.parse_args()
     if args.digest_of:
         for line in open(args.digest_of):
@@ -155,10 +157,12 @@ def main():
         else:
             key = (kw.get("num_blocks", 3), kw.get("language_model", "t5-base"))
             if key not in sds:
-                sds[key] = pkg.synthetic.make_state_dict("resnet50", seed=0, num_attention_blocks=key[0],
+                sds[key] = pkg.synthetic.make_state_dict(args.vision, seed=0, num_attention_blocks=key[0],
                                                          language_model=key[1])
-            eng = pkg.engine.VQAEngine(sds[key], vision="resnet50", batch=2, seq_len=16, image_size=64,
+            eng = pkg.engine.VQAEngine(sds[key], vision=args.vision, batch=2, seq_len=16, image_size=64,
                                        device=args.device, **kw)
+            if args.vision != "resnet50":
+                name = f"{args.vision}_{name}"
         print(json.dumps({"config": name, **signature(pkg, eng)}, sort_keys=True))
         del eng
 
