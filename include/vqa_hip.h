@@ -395,6 +395,27 @@ typedef struct {
 } vqa_image_desc;
 int vqa_resize_linear_u8(const void* src, const vqa_image_desc* desc, int batch, int oh, int ow, float* out,
                          hipStream_t stream);
+/* The ViT collate's image path (dataset_utils/vit_vqa_daquar_dataset.py:133-138: ViTImageProcessor =
+ * PIL resize(BILINEAR) to oh x ow, rescale 1/255, normalise) for a whole batch, bit-equal to Pillow
+ * (image_pil.hip): Pillow's antialiased two-pass 8-bit resample, horizontal pass first, then
+ * out[b][c][y][x] = lut[c][v] (lut: 3 x 256 fp32, device).  `src` is packed as for
+ * vqa_resize_linear_u8; desc[b] (device memory) also says where the image's coefficient tables
+ * start in `tables` (device int32) and their row length: the table of an axis `in -> out` is
+ * {first source index, taps}[out] followed by k[out][ksize], Pillow's 22-bit fixed-point
+ * coefficients, computed on the host (data.pil_bilinear_coeffs).  max_h, max_w: the largest
+ * source sides of the batch (<= 8192).  work: the uint8 intermediate [batch][max_h][ow][3],
+ * work_stride (>= max_h * ow * 3) bytes per image.  Two kernels on `stream`, no atomics.
+ * Images with h > 100 * w and oh < h are outside the contract: Pillow resamples those
+ * vertical pass first. */
+typedef struct {
+  long long offset;        /* byte offset of the image in src */
+  int h, w;                /* source size (>= 1) */
+  int xtab, ytab;          /* offsets (in ints) of the w -> ow and h -> oh tables in `tables` */
+  int xk, yk;              /* their ksize */
+} vqa_pil_image_desc;
+int vqa_resize_pil_bilinear_u8(const void* src, const vqa_pil_image_desc* desc, int batch, int max_h, int max_w,
+                               int oh, int ow, const int* tables, const float* lut, void* work,
+                               long long work_stride, float* out, hipStream_t stream);
 /* deterministic, no atomics: each touched row gets its tokens' dh rows summed in token order
  * and ADDED to it (the rows must be zero, or hold an earlier partial sum); any number of
  * tokens (slices of 16384, in order); ws = 3*min(tokens, 16384) ints */

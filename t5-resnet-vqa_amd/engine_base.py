@@ -113,19 +113,29 @@ def batch_rows(batch, key, planned, allow_empty=False):
     return n
 
 
+def _is_rows_of(dst, src, n):
+    """src already is the first n rows of the buffer dst (a collate wrote them in place, e.g.
+    DaquarVitCollate(out=eng.PIX)): nothing to copy."""
+    return (isinstance(src, torch.Tensor) and src.device == dst.device and src.dtype == dst.dtype
+            and src.data_ptr() == dst.data_ptr() and src.is_contiguous() and dst.is_contiguous()
+            and tuple(src.shape) == (n,) + tuple(dst.shape[1:]))
+
+
 def load_rows(dst, src, n, fill=None, empty_fill=0):
     """dst[:n] <- src (n rows); the planned rows past n are padding: copies of rows 0..n-1
     (real samples, so every activation stays finite) or `fill` (targets: IGNORE_INDEX, so the
     padded rows add nothing to the loss or to any gradient -- the NLL mean runs over the n
     real rows).  n = 0 (an empty data-parallel rank): every row is `fill`, else `empty_fill`
-    (finite inputs whose targets are all ignored: the rank's gradient is exactly zero)."""
+    (finite inputs whose targets are all ignored: the rank's gradient is exactly zero).
+    A src that is dst's own first n rows is not copied onto itself."""
     if src is None:
         return
     B = dst.shape[0]
     if n == 0:
         dst.fill_(fill if fill is not None else empty_fill)
         return
-    _h2d(dst[:n] if n < B else dst, src)
+    if not _is_rows_of(dst, src, n):
+        _h2d(dst[:n] if n < B else dst, src)
     if n == B:
         return
     if fill is not None:

@@ -62,6 +62,13 @@ class ImageDesc(ctypes.Structure):
     _fields_ = [("offset", c_ll), ("h", c_int), ("w", c_int)]
 
 
+class PilImageDesc(ctypes.Structure):
+    """vqa_pil_image_desc: ImageDesc + the offsets (in ints) and row lengths of the image's x and y
+    coefficient tables."""
+    _fields_ = [("offset", c_ll), ("h", c_int), ("w", c_int), ("xtab", c_int), ("ytab", c_int), ("xk", c_int),
+                ("yk", c_int)]
+
+
 class ColsumJob(ctypes.Structure):
     _fields_ = [("ws", c_void_p), ("out", c_void_p), ("stride", c_ll), ("parts", c_int), ("cols", c_int),
                 ("beta", c_float), ("first_block", c_int)]
@@ -210,6 +217,7 @@ register("vqa_colsum_partials", P, c_int, c_ll, c_int, P, c_float)
 register("vqa_image_to_nhwc8", P, P, c_int, c_int, c_int)
 register("vqa_image_to_s2d16", P, P, c_int, c_int, c_int)
 register("vqa_resize_linear_u8", P, P, c_int, c_int, c_int, P)
+register("vqa_resize_pil_bilinear_u8", P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_ll, P)
 register("vqa_maxpool3x3s2_nhwc", P, P, c_int, c_int, c_int, c_int, c_int, c_int)
 register("vqa_subsample_nhwc", P, c_int, c_int, c_int, c_int, c_int, P, c_ll)
 register("vqa_stem_s2d_conv", P, P, P, P, c_int, c_int, c_int)
