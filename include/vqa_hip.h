@@ -146,8 +146,8 @@ typedef struct vqa_gemm_desc {
    * and B (a_trans = b_trans = 0) with no a_conv / b_conv, splitk <= 1, no mask16, the
    * vectorised epilogue (n, ld*, strides multiples of 8, 16-byte aligned pointers), norm_w /
    * norm_b / norm_y32 16-byte and norm_y16 8-byte aligned with strides multiples of 4,
-   * config 0 or one of 3, 4, 5, 6, 7, 21, and batch * ceil(m / BM) <= 16384 (BM = the rows
-   * of the tile config that runs, vqa_gemm_select).
+   * config 0 or one with the NORM flag of VQA_GEMM_TILE_TABLE, and batch * ceil(m / BM) <= 16384
+   * (BM = the rows of the tile config that runs, vqa_gemm_select).
    * LayerNorm: norm_b, norm_mean, norm_rstd required, no norm_drop.  RMSNorm: norm_b and
    * norm_mean NULL; norm_drop needs batch 1.  Anything else is VQA_ERR_INVALID, nothing written.
    * workspace: >= vqa_gemm_workspace_bytes(d) = the 64 KiB counter block split-K uses, one
@@ -165,15 +165,56 @@ typedef struct vqa_gemm_desc {
   vqa_dropout norm_drop;
 } vqa_gemm_desc;
 
-/* tile configs: 1 128x128/3 stages, 2 128x64/4, 3 64x64/4, 4 64x64/2, 5 64x64/3, 6 128x64/2,
- * 7 64x128/2, 8 128x128/2 (4 waves); 9 256x128/2, 10 128x256/2, 11 256x256/2, 12 256x128/3 (8 waves);
- * 13..16 64x192 / 128x192 (k-contiguous B only); 17..20 the LDS-patch convolution;
- * 21 64x64/2, 22 64x128/2, 23 128x64/2 with 128-deep k-tiles (no implicit im2col, no split-K);
- * 24 64x128/2 with 8 waves (2x4) and 128-deep k-tiles; 25 the LDS-patch convolution's 128x128 tile
- * with 8 waves (4x2); 26 64x128, 27 128x64, 28 64x64 for k <= 64 only (one k-tile in a single-stage
- * ring: more workgroups per CU; no implicit im2col) */
+/* The tile configs: one row per config id 1..VQA_GEMM_CONFIGS,
+ *   X(id, BM, BN, LDS stages, waves_m, waves_n, k-tile depth, flags)
+ * a BM x BN output tile on waves_m x waves_n waves of 64 lanes.  This table is the only place that
+ * says which configs exist and what each accepts: the library's dispatch, eligibility check and
+ * workspace sizing expand it, and the Python bindings parse these rows (lib.py).  Flags:
+ *   PATCH  the LDS-patch 3x3 convolution (a_conv = 2) and nothing else
+ *   KC_B   needs a k-contiguous B operand (b_trans = 0): the 192-column tiles
+ *   K1     one k-tile in a single-stage ring: k <= 64 only (more workgroups per CU)
+ *   FP8    has an e4m3 form (vqa_gemm_desc.fp8)
+ *   NORM   has a row-norm tail (vqa_gemm_desc.norm), in bf16 and in e4m3
+ *   PAIR   usable in vqa_gemm_pair
+ * Derived: a 128-deep or K1 config takes no implicit-im2col operand (a_conv = 1, b_conv); a
+ * 128-deep, K1 or PATCH config takes no split-K. */
+#define VQA_TILE_PATCH 1
+#define VQA_TILE_KC_B 2
+#define VQA_TILE_K1 4
+#define VQA_TILE_FP8 8
+#define VQA_TILE_NORM 16
+#define VQA_TILE_PAIR 32
+#define VQA_GEMM_TILE_TABLE(X)                                             \
+  X(1, 128, 128, 3, 2, 2, 64, VQA_TILE_FP8)                                \
+  X(2, 128, 64, 4, 2, 2, 64, VQA_TILE_FP8)                                 \
+  X(3, 64, 64, 4, 2, 2, 64, VQA_TILE_FP8 | VQA_TILE_NORM | VQA_TILE_PAIR)  \
+  X(4, 64, 64, 2, 2, 2, 64, VQA_TILE_FP8 | VQA_TILE_NORM | VQA_TILE_PAIR)  \
+  X(5, 64, 64, 3, 2, 2, 64, VQA_TILE_FP8 | VQA_TILE_NORM)                  \
+  X(6, 128, 64, 2, 2, 2, 64, VQA_TILE_FP8 | VQA_TILE_NORM | VQA_TILE_PAIR) \
+  X(7, 64, 128, 2, 2, 2, 64, VQA_TILE_FP8 | VQA_TILE_NORM | VQA_TILE_PAIR) \
+  X(8, 128, 128, 2, 2, 2, 64, VQA_TILE_FP8)                                \
+  X(9, 256, 128, 2, 4, 2, 64, VQA_TILE_FP8)                                \
+  X(10, 128, 256, 2, 2, 4, 64, VQA_TILE_FP8)                               \
+  X(11, 256, 256, 2, 2, 4, 64, 0)                                          \
+  X(12, 256, 128, 3, 4, 2, 64, VQA_TILE_FP8)                               \
+  X(13, 64, 192, 2, 2, 2, 64, VQA_TILE_KC_B)                               \
+  X(14, 128, 192, 2, 2, 2, 64, VQA_TILE_KC_B)                              \
+  X(15, 64, 192, 3, 2, 2, 64, VQA_TILE_KC_B)                               \
+  X(16, 128, 192, 3, 2, 2, 64, VQA_TILE_KC_B)                              \
+  X(17, 128, 64, 2, 2, 2, 64, VQA_TILE_PATCH)                              \
+  X(18, 128, 128, 2, 2, 2, 64, VQA_TILE_PATCH)                             \
+  X(19, 64, 64, 2, 2, 2, 64, VQA_TILE_PATCH)                               \
+  X(20, 64, 128, 2, 2, 2, 64, VQA_TILE_PATCH)                              \
+  X(21, 64, 64, 2, 2, 2, 128, VQA_TILE_FP8 | VQA_TILE_NORM)                \
+  X(22, 64, 128, 2, 2, 2, 128, VQA_TILE_FP8)                               \
+  X(23, 128, 64, 2, 2, 2, 128, VQA_TILE_FP8)                               \
+  X(24, 64, 128, 2, 2, 4, 128, 0)                                          \
+  X(25, 128, 128, 3, 4, 2, 64, VQA_TILE_PATCH)                             \
+  X(26, 64, 128, 1, 2, 2, 64, VQA_TILE_K1)                                 \
+  X(27, 128, 64, 1, 2, 2, 64, VQA_TILE_K1)                                 \
+  X(28, 64, 64, 1, 2, 2, 64, VQA_TILE_K1)
 #define VQA_GEMM_CONFIGS 28
-#define VQA_GEMM_PATCH_FIRST 17    /* configs 17..20 and VQA_GEMM_PATCH_WIDE: a_conv = 2 only */
+#define VQA_GEMM_PATCH_FIRST 17    /* the PATCH rows: FIRST..LAST and WIDE (a_conv = 2 only) */
 #define VQA_GEMM_PATCH_LAST 20
 #define VQA_GEMM_PATCH_WIDE 25
 int vqa_gemm(const vqa_gemm_desc* d, hipStream_t stream);
@@ -189,9 +230,10 @@ int vqa_gemm_select(const vqa_gemm_desc* d);
 long long vqa_gemm_workspace_bytes(const vqa_gemm_desc* d);
 /* Two independent GEMMs in one launch: a layer's input gradient dX (a_trans=0,
  * b_trans=1) and weight gradient dW (a_trans=1, b_trans=1), both batch 1, no
- * conv.  Each keeps its own epilogue and tile config (configs 3, 4, 6, 7; others
- * map to 4).  Any other pair of descriptors runs as two vqa_gemm calls.  A descriptor with
- * norm != 0 is rejected (VQA_ERR_INVALID): the paired kernel has no norm tail. */
+ * conv.  Each keeps its own epilogue and tile config (the configs with the PAIR flag of
+ * VQA_GEMM_TILE_TABLE; others map to 4).  Any other pair of descriptors runs as two vqa_gemm
+ * calls.  A descriptor with norm != 0 is rejected (VQA_ERR_INVALID): the paired kernel has no
+ * norm tail. */
 int vqa_gemm_pair(const vqa_gemm_desc* dx, const vqa_gemm_desc* dw, hipStream_t stream);
 
 /* ------------------------------------------------------------- attention ---

@@ -223,8 +223,11 @@ static int conv_patch_dispatch(GemmParams& P, int config, hipStream_t s) {
               "vqa_gemm(a_conv=2): a 3x3 / stride-1 / pad-1 convolution is required");
   VQA_REQUIRE(g.c % 64 == 0 && P.k == 9 * g.c && P.m == g.n * g.h * g.w, "vqa_gemm(a_conv=2): C %% 64, K = 9C, M = NHW");
   VQA_REQUIRE(P.splitk <= 1 && P.alpha == 1.f, "vqa_gemm(a_conv=2): no split-K, alpha = 1");
-  int bm = (config == 19 || config == 20) ? 64 : 128;
-  const int bn = (config == 18 || config == 20 || config == 25) ? 128 : 64;
+  VQA_REQUIRE(config >= 1 && config <= VQA_GEMM_CONFIGS && TILES[config].has(VQA_TILE_PATCH),
+              "vqa_gemm(a_conv=2): tile config %d is not an LDS-patch config", config);
+  const Tile& t = TILES[config];
+  int bm = t.bm;
+  const int bn = t.bn;
   // a 128-row tile whose input patch exceeds the LDS buffer (e.g. C >= 128 at W 40-42 or 51-64,
   // where R = 128 / W leaves (R + 2)(W + 2) > PMAX_DB) runs as the 64-row tile: the tile
   // configs give the same bits, so this changes speed only
@@ -237,10 +240,10 @@ static int conv_patch_dispatch(GemmParams& P, int config, hipStream_t s) {
   G.pins = vqa::cdiv(G.npix, 8);
   G.chunks = g.c / 64;
   G.ppart = vqa::cdiv(G.pins, 10 - 3);          // double-buffered: parts on taps S-1..8 at S = 3 stages
-  // config 25: 8 waves -- 4 x 2 on the 128 x 128 tile (the layer2 / layer3 3x3 convs: 31.8 vs
+  // the 8-wave tile: 4 x 2 on 128 x 128 (the layer2 / layer3 3x3 convs: 31.8 vs
   // 36.6 us at 14 x 14 x 256, 35.7 vs 38.5 at 28 x 28 x 128, profiles/r05_conv_patch_micro.txt),
   // 2 x 4 when the patch needs the 64-row tile
-  if (config == 25) return bm == 128 ? launch_patch<128, 128, 4, 2>(P, G, s) : launch_patch<64, 128, 2, 4>(P, G, s);
+  if (t.wm * t.wn == 8) return bm == 128 ? launch_patch<128, 128, 4, 2>(P, G, s) : launch_patch<64, 128, 2, 4>(P, G, s);
   if (bm == 128 && bn == 64) return launch_patch<128, 64>(P, G, s);
   if (bm == 128) return launch_patch<128, 128>(P, G, s);
   if (bn == 64) return launch_patch<64, 64>(P, G, s);

@@ -53,17 +53,31 @@ __global__ __launch_bounds__(256) void gemm_pair_kernel(GemmParams P1, GemmParam
   }
 }
 
-// config: 0 = auto; 1 = 128x128 (3 stages); 2 = 128x64 (4); 3 = 64x64 (4); 4 = 64x64 (2);
-//         5 = 64x64 (3); 6 = 128x64 (2); 7 = 64x128 (2); 8 = 128x128 (2)  -- 4 waves (2x2);
-//         9 = 256x128 (2, 8 waves 4x2); 10 = 128x256 (2, 8 waves 2x4); 11 = 256x256 (2, 8 waves 2x4);
-//         12 = 256x128 (3, 8 waves 4x2); 13 = 64x192 (2); 14 = 128x192 (2); 15 = 64x192 (3);
-//         16 = 128x192 (3) -- 4 waves, k-contiguous B only;
-//         17..20 = the LDS-patch 3x3 convolution (a_conv = 2, conv_patch.inl): 128x64, 128x128,
-//         64x64, 64x128; 21..23 = 64x64 / 64x128 / 128x64 with 128-deep k-tiles (4 waves);
-//         24 = 64x128 with 128-deep k-tiles on 8 waves (2x4); 26 / 27 / 28 = 64x128 / 128x64 /
-//         64x64 for k <= 64 (one k-tile, single-stage ring: 4 / 4 / 5 workgroups per CU).
-// Every config accumulates each output element in the same K order (BK = 64
-// k-tiles, 16-deep MFMA steps), so the choice changes speed, never the bits.
+// Why some rows of VQA_GEMM_TILE_TABLE exist (the kernels behind them: run_tile, gemm_body.h):
+//   192-column tiles (KC_B): one tile per CU for the transformer shapes (2048 x 3072 = 16 x 16
+//     tiles of 128 x 192).
+//   128-deep k-tiles: twice the bytes per ring slot and per barrier (the per-k-tile fixed cost of
+//     the L2 -> LDS fill is amortised over 32-48 KB instead of 16-24 KB).  The 8-wave one is the
+//     64x128 tile on 2x4 waves of 32x32: twice the waves issuing the ring's DMA pieces (r04
+//     stamps: 7 % faster on the 2048 x 2304 x 768 q|k|v projection).
+//   K1: one k-tile in a single-stage ring (gemm_k1_kernel): 4 / 4 / 5 workgroups per CU.
+//   No e4m3 form of 256x256: its double-buffered 32-B fragments would spill.
+constexpr bool tile_table_matches_defines() {
+  for (int c = 1; c <= VQA_GEMM_CONFIGS; ++c) {
+    const bool patch = (c >= VQA_GEMM_PATCH_FIRST && c <= VQA_GEMM_PATCH_LAST) || c == VQA_GEMM_PATCH_WIDE;
+    if (TILES[c].id != c || TILES[c].has(VQA_TILE_PATCH) != patch) return false;
+  }
+  return true;
+}
+static_assert(sizeof(TILES) / sizeof(Tile) == VQA_GEMM_CONFIGS + 1, "VQA_GEMM_CONFIGS != rows of VQA_GEMM_TILE_TABLE");
+static_assert(tile_table_matches_defines(),
+              "VQA_GEMM_TILE_TABLE: ids must be 1..VQA_GEMM_CONFIGS in order, PATCH rows = VQA_GEMM_PATCH_*");
+// 64x64 / 2 stages: what an e4m3 descriptor runs on auto (config 0), and what the paired launch
+// runs for a config it has no kernel for
+constexpr int CFG_SMALL = 4;
+static_assert(TILES[CFG_SMALL].has(VQA_TILE_FP8) && TILES[CFG_SMALL].has(VQA_TILE_NORM) &&
+                  TILES[CFG_SMALL].has(VQA_TILE_PAIR), "the fallback tile must exist in every form");
+
 // Auto (measured on MI355X, tools/callprof.py): fewer stages = less LDS = more
 // resident blocks, which beats a deep ring at this model's sizes; 128-wide
 // tiles only pay for narrow-N, long-K convolutions.  Engines autotune per call.
@@ -76,72 +90,7 @@ int auto_config(int m, int n, int k, int batch) {
   return 4;
 }
 
-template <bool AKC, bool BKC, bool GA, bool GB>
-int dispatch_tile(GemmParams& P, int batch, int config, hipStream_t s) {
-  if (config == 0) config = auto_config(P.m, P.n, P.k, batch);
-  switch (config) {
-    case 1: return launch<128, 128, 3, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-    case 2: return launch<128, 64, 4, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-    case 4: return launch<64, 64, 2, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-    case 5: return launch<64, 64, 3, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-    case 6: return launch<128, 64, 2, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-    case 7: return launch<64, 128, 2, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-    case 8: return launch<128, 128, 2, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-    case 9: return launch<256, 128, 2, 4, 2, AKC, BKC, GA, GB>(P, batch, s);
-    case 10: return launch<128, 256, 2, 2, 4, AKC, BKC, GA, GB>(P, batch, s);
-    case 11: return launch<256, 256, 2, 2, 4, AKC, BKC, GA, GB>(P, batch, s);
-    case 12: return launch<256, 128, 3, 4, 2, AKC, BKC, GA, GB>(P, batch, s);
-    case 13: case 14: case 15: case 16:
-      // 192-column tiles: one tile per CU for the transformer shapes (2048 x 3072 = 16 x 16 tiles
-      // of 128 x 192); the n-contig (transposed-B) LDS image has no 192-row form
-      if constexpr (BKC) {
-        if (config == 13) return launch<64, 192, 2, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-        if (config == 14) return launch<128, 192, 2, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-        if (config == 15) return launch<64, 192, 3, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-        return launch<128, 192, 3, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-      } else {
-        return vqa::fail(VQA_ERR_INVALID, "vqa_gemm: tile config %d needs a k-contiguous B operand (b_trans=0)", config);
-      }
-    case 21: case 22: case 23: case 24:
-      // 128-deep k-tiles: twice the bytes per ring slot and per barrier (the per-k-tile fixed
-      // cost of the L2 -> LDS fill is amortised over 32-48 KB instead of 16-24 KB); plain
-      // (non-gathered) operands, no split-K.  24: config 22's 64x128 tile on 8 waves (2x4, each
-      // 32x32): twice the waves issuing the ring's DMA pieces (r04 stamps: 7 % faster on the
-      // 2048 x 2304 x 768 q|k|v projection)
-      if constexpr (!GA && !GB) {
-        if (config == 21) return launch<64, 64, 2, 2, 2, AKC, BKC, GA, GB, 128>(P, batch, s);
-        if (config == 22) return launch<64, 128, 2, 2, 2, AKC, BKC, GA, GB, 128>(P, batch, s);
-        if (config == 24) return launch<64, 128, 2, 2, 4, AKC, BKC, GA, GB, 128>(P, batch, s);
-        return launch<128, 64, 2, 2, 2, AKC, BKC, GA, GB, 128>(P, batch, s);
-      } else {
-        return vqa::fail(VQA_ERR_INVALID, "vqa_gemm: tile config %d takes no implicit-im2col operand", config);
-      }
-    case 26: case 27: case 28:
-      // one k-tile in a single-stage ring (gemm_k1_kernel): k <= 64, plain operands
-      if constexpr (!GA && !GB) {
-        if (config == 26) return launch_k1<64, 128, 4, AKC, BKC, GA, GB>(P, batch, s);
-        if (config == 27) return launch_k1<128, 64, 4, AKC, BKC, GA, GB>(P, batch, s);
-        return launch_k1<64, 64, 5, AKC, BKC, GA, GB>(P, batch, s);
-      } else {
-        return vqa::fail(VQA_ERR_INVALID, "vqa_gemm: tile config %d takes no implicit-im2col operand", config);
-      }
-    default: return launch<64, 64, 4, 2, 2, AKC, BKC, GA, GB>(P, batch, s);
-  }
-}
-
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// (BM, BN) of a tile config (dispatch_tile's table)
-void tile_of(int config, int& bm, int& bn) {
-  static const int T[VQA_GEMM_CONFIGS + 1][2] = {{64, 64},   {128, 128}, {128, 64}, {64, 64},  {64, 64},
-                                                 {64, 64},   {128, 64},  {64, 128}, {128, 128}, {256, 128},
-                                                 {128, 256}, {256, 256}, {256, 128}, {64, 192}, {128, 192},
-                                                 {64, 192},  {128, 192}, {128, 64}, {128, 128}, {64, 64},
-                                                 {64, 128},  {64, 64},   {64, 128}, {128, 64}, {64, 128},
-                                                 {128, 128}, {64, 128},  {128, 64}, {64, 64}};
-  bm = T[config][0];
-  bn = T[config][1];
-}
 
 // slices actually launched: whole k-tiles per slice, no empty slice
 int effective_splitk(int k, int splitk, int* kper) {
@@ -165,32 +114,49 @@ int patch_auto_config(const vqa_gemm_desc* d) {
   const int bm64 = d->ga.w <= 8;
   return d->n <= 64 ? (bm64 ? 19 : 17) : (bm64 ? 20 : 18);
 }
-}  // namespace
 
-namespace {
-// auto tile of a norm descriptor: only configs with a norm tail (e4m3: the 64x64 / 2 tile, as
-// vqa_gemm runs config 0 there)
+// auto tile of a norm descriptor: only configs with a norm tail
 int norm_auto_config(const vqa_gemm_desc* d) {
-  if (d->fp8) return 4;
+  if (d->fp8) return CFG_SMALL;
   const int c = auto_config(d->m, d->n, d->k, d->batch);
-  return c == 3 || c == 4 ? c : 3;
+  return TILES[c].has(VQA_TILE_NORM) ? c : 3;
 }
-}  // namespace
 
-extern "C" int vqa_gemm_select(const vqa_gemm_desc* d) {
-  if (!d) return 0;
+// the tile config this descriptor runs: vqa_gemm, vqa_gemm_select, the workspace size and the
+// norm counters all ask here
+int resolve_config(const vqa_gemm_desc* d) {
   if (d->config) return d->config;
   if (d->norm) return norm_auto_config(d);
-  return d->a_conv == 2 ? patch_auto_config(d) : auto_config(d->m, d->n, d->k, d->batch);
+  if (d->a_conv == 2) return patch_auto_config(d);
+  if (d->fp8) return CFG_SMALL;
+  return auto_config(d->m, d->n, d->k, d->batch);
 }
+
+// Does tile t take descriptor d (P: prepare()'s view of it)?  Every refusal of a (tile,
+// descriptor) combination, made before anything is launched.
+int check_tile(const Tile& t, const vqa_gemm_desc* d, const GemmParams& P) {
+  if (d->relu >= 2 && d->a_conv != 2) {                    // GELU / tanh: gemm_ext_kernel's one tile, whatever the config
+    VQA_REQUIRE(!t.has(VQA_TILE_PATCH), "vqa_gemm: tile config %d is for a_conv = 2 only", t.id);
+    return VQA_OK;
+  }
+  const char* why = tile_lacks(t, !d->b_trans, d->a_conv || d->b_conv, d->fp8 != 0, d->norm != 0, d->a_conv == 2);
+  VQA_REQUIRE(why == nullptr, "vqa_gemm: tile config %d %s", t.id, why);
+  VQA_REQUIRE(!t.has(VQA_TILE_K1) || P.k <= BK, "vqa_gemm: tile config %d takes one k-tile (k <= %d)", t.id, BK);
+  VQA_REQUIRE(!t.no_splitk() || P.splitk <= 1, "vqa_gemm: tile config %d takes no split-K", t.id);
+  return VQA_OK;
+}
+}  // namespace
+
+extern "C" int vqa_gemm_select(const vqa_gemm_desc* d) { return d ? resolve_config(d) : 0; }
 
 extern "C" long long vqa_gemm_workspace_bytes(const vqa_gemm_desc* d) {
   if (d && d->norm) return NORM_CNT_BYTES;               // one arrival counter per (batch, row block)
   if (!d || d->splitk <= 1 || d->a_conv == 2) return 0;
-  int bm, bn, kper;
-  tile_of(vqa_gemm_select(d), bm, bn);
+  const int cfg = resolve_config(d);
+  if (cfg < 1 || cfg > VQA_GEMM_CONFIGS) return 0;        // no such tile: vqa_gemm refuses the descriptor
+  int kper;
   const int S = effective_splitk(d->fp8 ? d->k / 2 : d->k, d->splitk, &kper);   // fp8: k in 2-byte units
-  return splitk_bytes(bm, bn, d->m, d->n, d->batch < 1 ? 1 : d->batch, S);
+  return splitk_bytes(TILES[cfg].bm, TILES[cfg].bn, d->m, d->n, d->batch < 1 ? 1 : d->batch, S);
 }
 
 static int prepare(const vqa_gemm_desc* d, GemmParams& P) {
@@ -291,11 +257,7 @@ static int prepare_norm(const vqa_gemm_desc* d, const GemmParams& P, NormParams&
   VQA_REQUIRE(P.vec, "vqa_gemm(norm): needs the vectorised epilogue (ld*, strides multiples of 8, aligned pointers)");
   VQA_REQUIRE(d->workspace && aligned16(d->workspace) && d->workspace_bytes >= NORM_CNT_BYTES,
               "vqa_gemm(norm): needs a 16-byte aligned workspace of >= %lld bytes", NORM_CNT_BYTES);
-  const int cfg = d->config;
-  VQA_REQUIRE(cfg == 0 || (cfg >= 3 && cfg <= 7) || cfg == 21,
-              "vqa_gemm(norm): tile config %d has no norm tail (0, 3-7, 21)", cfg);
-  int bm, bn;                                             // one counter per (batch, row block of the tile's BM rows)
-  tile_of(cfg ? cfg : norm_auto_config(d), bm, bn);
+  const int bm = TILES[resolve_config(d)].bm;             // one counter per (batch, row block of the tile's BM rows)
   VQA_REQUIRE((long long)vqa::cdiv(d->m, bm) * d->batch <= NORM_MAX_BLOCKS,
               "vqa_gemm(norm): %lld (batch, row block) pairs at %d-row tiles, needs <= %lld",
               (long long)vqa::cdiv(d->m, bm) * d->batch, bm, NORM_MAX_BLOCKS);
@@ -329,23 +291,19 @@ int vqa_gemm_norm_dispatch(void* P, void* Q, int batch, int config, int fp8, hip
 extern "C" int vqa_gemm(const vqa_gemm_desc* d, hipStream_t stream) {
   GemmParams P;
   if (int rc = prepare(d, P)) return rc;
-  const int batch = d->batch, cfg = d->config;
+  const int batch = d->batch, cfg = resolve_config(d);
+  if (int rc = check_tile(TILES[cfg], d, P)) return rc;
   if (d->norm) {                                          // GEMM + row norm (gemm_norm_kernel)
     NormParams Q;
     if (int rc = prepare_norm(d, P, Q)) return rc;
-    const int nc = cfg ? cfg : norm_auto_config(d);           // auto: only configs with a norm tail
-    return vqa_gemm_norm_dispatch(&P, &Q, batch, nc, d->fp8 != 0, stream);
+    return vqa_gemm_norm_dispatch(&P, &Q, batch, cfg, d->fp8 != 0, stream);
   }
   if (d->fp8) return vqa_gemm_fp8_dispatch(&P, batch, cfg, stream);
   const bool akc = !d->a_trans, bkc = !d->b_trans;
-  const bool patch_cfg = (cfg >= VQA_GEMM_PATCH_FIRST && cfg <= VQA_GEMM_PATCH_LAST) || cfg == VQA_GEMM_PATCH_WIDE;
   if (d->a_conv == 2) {                                   // LDS-patch 3x3 convolution (conv_patch.inl)
     VQA_REQUIRE(akc && bkc && !d->b_conv && batch == 1, "vqa_gemm(a_conv=2): k-contiguous B, batch 1");
-    VQA_REQUIRE(cfg == 0 || patch_cfg, "vqa_gemm(a_conv=2): tile config %d is not a patch config (%d..%d)", cfg,
-                VQA_GEMM_PATCH_FIRST, VQA_GEMM_PATCH_LAST);
-    return conv_patch_dispatch(P, vqa_gemm_select(d), stream);
+    return conv_patch_dispatch(P, cfg, stream);
   }
-  VQA_REQUIRE(!patch_cfg, "vqa_gemm: tile config %d is for a_conv = 2 only", cfg);
   if (d->relu >= 2) {                                     // GELU / tanh: gemm_ext_kernel only
     VQA_REQUIRE(akc && bkc && !d->a_conv && !d->b_conv && P.splitk <= 1,
                 "vqa_gemm: GELU / tanh epilogues need k-contiguous A and B, no conv operand, no split-K");
@@ -365,37 +323,29 @@ extern "C" int vqa_gemm(const vqa_gemm_desc* d, hipStream_t stream) {
 }
 
 namespace {
-// tile configs available to the paired launch (a subset of dispatch_tile's)
-template <int C> struct CfgOf;
-template <> struct CfgOf<3> { static constexpr int BM = 64, BN = 64, S = 4; };
-template <> struct CfgOf<4> { static constexpr int BM = 64, BN = 64, S = 2; };
-template <> struct CfgOf<6> { static constexpr int BM = 128, BN = 64, S = 2; };
-template <> struct CfgOf<7> { static constexpr int BM = 64, BN = 128, S = 2; };
-
+// the paired launch of two PAIR tiles
 template <int C1, int C2>
 int launch_pair(GemmParams& P1, GemmParams& P2, hipStream_t s) {
-  using X = CfgOf<C1>;
-  using Y = CfgOf<C2>;
-  P1.tiles_m = vqa::cdiv(P1.m, X::BM); P1.tiles_n = vqa::cdiv(P1.n, X::BN);
-  P2.tiles_m = vqa::cdiv(P2.m, Y::BM); P2.tiles_n = vqa::cdiv(P2.n, Y::BN);
+  constexpr Tile X = TILES[C1], Y = TILES[C2];
+  P1.tiles_m = vqa::cdiv(P1.m, X.bm); P1.tiles_n = vqa::cdiv(P1.n, X.bn);
+  P2.tiles_m = vqa::cdiv(P2.m, Y.bm); P2.tiles_n = vqa::cdiv(P2.n, Y.bn);
   const int t1 = P1.tiles_m * P1.tiles_n, t1pad = (t1 + 7) / 8 * 8;
   const int grid = t1pad + P2.tiles_m * P2.tiles_n;
-  hipLaunchKernelGGL((gemm_pair_kernel<X::BM, X::BN, X::S, Y::BM, Y::BN, Y::S>), dim3(grid), dim3(256), 0, s, P1, P2,
-                     t1pad);
+  hipLaunchKernelGGL((gemm_pair_kernel<X.bm, X.bn, X.stages, Y.bm, Y.bn, Y.stages>), dim3(grid), dim3(256), 0, s, P1,
+                     P2, t1pad);
   return vqa::check_launch("vqa_gemm_pair");
 }
 
-template <int C1>
-int pair_second(int c2, GemmParams& P1, GemmParams& P2, hipStream_t s) {
-  switch (c2) {
-    case 3: return launch_pair<C1, 3>(P1, P2, s);
-    case 6: return launch_pair<C1, 6>(P1, P2, s);
-    case 7: return launch_pair<C1, 7>(P1, P2, s);
-    default: return launch_pair<C1, 4>(P1, P2, s);
-  }
+// f(id) for a PAIR tile (pair_cfg has mapped every other config away)
+template <class F>
+int with_pair_tile(int config, F&& f) {
+  return with_tile(config, [&](auto c) {
+    if constexpr (TILES[decltype(c)::value].has(VQA_TILE_PAIR)) return f(c);
+    else return vqa::fail(VQA_ERR_INVALID, "vqa_gemm_pair: tile config %d has no paired kernel", decltype(c)::value);
+  });
 }
 
-int pair_cfg(int c) { return (c == 3 || c == 6 || c == 7) ? c : 4; }
+int pair_cfg(int c) { return TILES[c].has(VQA_TILE_PAIR) ? c : CFG_SMALL; }
 }  // namespace
 
 extern "C" int vqa_gemm_pair(const vqa_gemm_desc* dx, const vqa_gemm_desc* dw, hipStream_t stream) {
@@ -410,12 +360,11 @@ extern "C" int vqa_gemm_pair(const vqa_gemm_desc* dx, const vqa_gemm_desc* dw, h
     if (int rc = vqa_gemm(dx, stream)) return rc;
     return vqa_gemm(dw, stream);
   }
-  const int c1 = pair_cfg(vqa_gemm_select(dx)), c2 = pair_cfg(vqa_gemm_select(dw));
-  switch (c1) {
-    case 3: return pair_second<3>(c2, P1, P2, stream);
-    case 6: return pair_second<6>(c2, P1, P2, stream);
-    case 7: return pair_second<7>(c2, P1, P2, stream);
-    default: return pair_second<4>(c2, P1, P2, stream);
-  }
+  const int c1 = pair_cfg(resolve_config(dx)), c2 = pair_cfg(resolve_config(dw));
+  return with_pair_tile(c1, [&](auto a) {
+    return with_pair_tile(c2, [&](auto b) {
+      return launch_pair<decltype(a)::value, decltype(b)::value>(P1, P2, stream);
+    });
+  });
 }
 #endif  // VQA_GEMM_MICRO

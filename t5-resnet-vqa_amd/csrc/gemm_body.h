@@ -1,8 +1,10 @@
 // The GEMM tile body, its kernel and launcher, shared by gemm.hip (bf16 operands),
 // gemm_fp8.hip (e4m3 operands, BASELINE config 5's forward weight GEMMs) and gemm_norm.hip (the
 // NORM instantiations: a row norm behind the epilogue), which compile as separate translation
-// units.
+// units; and the tile-config table they all dispatch from.
 #pragma once
+#include <type_traits>
+
 #include "gemm_common.h"
 
 namespace {
@@ -313,5 +315,63 @@ int launch_k1(GemmParams& P, int batch, hipStream_t s) {
   return vqa::check_launch("vqa_gemm");
 }
 
+// The rows of VQA_GEMM_TILE_TABLE (include/vqa_hip.h), indexed by config id; [0] is no tile
+// (config 0 = auto).  Every config accumulates each output element in the same K order (16-deep
+// MFMA steps in increasing k), so the choice changes speed, never the bits.
+struct Tile {
+  int id, bm, bn, stages, wm, wn, bkt, flags;
+  constexpr bool has(int f) const { return (flags & f) != 0; }
+  // 128-deep k-tiles and the single-stage ring are built for plain operands (no implicit im2col)
+  constexpr bool plain_only() const { return bkt != BK || has(VQA_TILE_K1); }
+  // split-K slices are counted in 64-deep k-tiles; one k-tile has nothing to split
+  constexpr bool no_splitk() const { return plain_only() || has(VQA_TILE_PATCH); }
+  // amdgpu_waves_per_eu of gemm_k1_kernel: 24 KB of LDS = 4 workgroups per CU, 16 KB (64x64) = 5
+  constexpr int k1_waves() const { return bm * bn > 64 * 64 ? 4 : 5; }
+};
+#define VQA_TILE_ROW(id, bm, bn, stages, wm, wn, bkt, flags) {id, bm, bn, stages, wm, wn, bkt, flags},
+constexpr Tile TILES[] = {{}, VQA_GEMM_TILE_TABLE(VQA_TILE_ROW)};
+#undef VQA_TILE_ROW
+
+// Why tile `t` has no kernel for an operand form, or nullptr if it has one.  At compile time this
+// decides which kernels exist (run_tile, gemm_norm.hip); at run time it is the first half of
+// vqa_gemm's eligibility check (gemm.hip: check_tile), so the two cannot disagree.
+constexpr const char* tile_lacks(const Tile& t, bool bkc, bool im2col, bool f8, bool norm, bool patch) {
+  if (t.has(VQA_TILE_PATCH) != patch) return patch ? "is not an LDS-patch config" : "is for a_conv = 2 only";
+  if (norm && !t.has(VQA_TILE_NORM)) return "has no norm tail";
+  if (f8 && !t.has(VQA_TILE_FP8)) return "has no e4m3 form";
+  // 192-column tiles: the n-contig (transposed-B) LDS image has no 192-row form
+  if (t.has(VQA_TILE_KC_B) && !bkc) return "needs a k-contiguous B operand (b_trans=0)";
+  if (t.plain_only() && im2col) return "takes no implicit-im2col operand";
+  return nullptr;
+}
+
+// f(std::integral_constant<int, id>) for the table row of `config`: the one switch over the tiles
+template <class F>
+int with_tile(int config, F&& f) {
+  switch (config) {
+#define VQA_TILE_CASE(id, ...) case id: return f(std::integral_constant<int, id>{});
+    VQA_GEMM_TILE_TABLE(VQA_TILE_CASE)
+#undef VQA_TILE_CASE
+    default: return vqa::fail(VQA_ERR_INVALID, "vqa_gemm: no tile config %d (1..%d)", config, VQA_GEMM_CONFIGS);
+  }
+}
+
+// run tile config C on one operand layout: its kernel, or a refusal where it has none
+template <int C, bool AKC, bool BKC, bool GA, bool GB, bool F8 = false>
+int run_tile(GemmParams& P, int batch, hipStream_t s) {
+  constexpr Tile T = TILES[C];
+  constexpr const char* why = tile_lacks(T, BKC, GA || GB, F8, false, false);
+  if constexpr (why != nullptr)
+    return vqa::fail(VQA_ERR_INVALID, "vqa_gemm: tile config %d %s", C, why);
+  else if constexpr (T.has(VQA_TILE_K1))
+    return launch_k1<T.bm, T.bn, T.k1_waves(), AKC, BKC, GA, GB>(P, batch, s);
+  else
+    return launch<T.bm, T.bn, T.stages, T.wm, T.wn, AKC, BKC, GA, GB, T.bkt, F8>(P, batch, s);
+}
+
+template <bool AKC, bool BKC, bool GA, bool GB, bool F8 = false>
+int dispatch_tile(GemmParams& P, int batch, int config, hipStream_t s) {
+  return with_tile(config, [&](auto c) { return run_tile<decltype(c)::value, AKC, BKC, GA, GB, F8>(P, batch, s); });
+}
 
 }  // namespace

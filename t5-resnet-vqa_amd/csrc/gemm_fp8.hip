@@ -14,13 +14,6 @@
 
 namespace {
 
-template <int BM, int BN, int ST, int NWM, int NWN, int BKT = BK>
-struct F8Tile {
-  static int run(GemmParams& P, int batch, hipStream_t s) {
-    return launch<BM, BN, ST, NWM, NWN, true, true, false, false, BKT, true>(P, batch, s);
-  }
-};
-
 // e4m3 of an fp32 value already scaled into [-448, 448]: round to nearest even (the
 // hardware conversion; torch.float8_e4m3fn rounds the same way)
 __device__ __forceinline__ uint32_t pack4_fp8(float a, float b, float c, float d) {
@@ -77,24 +70,7 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const void* __restrict_
 // both translation units see the same GemmParams layout from gemm_common.h)
 int vqa_gemm_fp8_dispatch(void* pp, int batch, int config, hipStream_t s) {
   GemmParams& P = *static_cast<GemmParams*>(pp);
-  switch (config) {
-    case 1: return F8Tile<128, 128, 3, 2, 2>::run(P, batch, s);
-    case 2: return F8Tile<128, 64, 4, 2, 2>::run(P, batch, s);
-    case 3: return F8Tile<64, 64, 4, 2, 2>::run(P, batch, s);
-    case 5: return F8Tile<64, 64, 3, 2, 2>::run(P, batch, s);
-    case 6: return F8Tile<128, 64, 2, 2, 2>::run(P, batch, s);
-    case 7: return F8Tile<64, 128, 2, 2, 2>::run(P, batch, s);
-    case 8: return F8Tile<128, 128, 2, 2, 2>::run(P, batch, s);
-    case 9: return F8Tile<256, 128, 2, 4, 2>::run(P, batch, s);
-    case 10: return F8Tile<128, 256, 2, 2, 4>::run(P, batch, s);
-    case 12: return F8Tile<256, 128, 3, 4, 2>::run(P, batch, s);
-    case 21: return F8Tile<64, 64, 2, 2, 2, 128>::run(P, batch, s);
-    case 22: return F8Tile<64, 128, 2, 2, 2, 128>::run(P, batch, s);
-    case 23: return F8Tile<128, 64, 2, 2, 2, 128>::run(P, batch, s);
-    case 0: case 4: return F8Tile<64, 64, 2, 2, 2>::run(P, batch, s);
-    default:   // 11 (256x256): its double-buffered 32-B fragments would spill; 13-20: bf16 / patch only
-      return vqa::fail(VQA_ERR_INVALID, "vqa_gemm(fp8): tile config %d has no e4m3 form", config);
-  }
+  return dispatch_tile<true, true, false, false, true>(P, batch, config, s);   // the FP8 rows of the tile table
 }
 
 extern "C" int vqa_quant_rows_fp8(const void* x, int x_bf16, long long ldx, int rows, int cols, void* q, long long ldq,

@@ -9,9 +9,7 @@
 // nothing can hang) with the row arithmetic the stand-alone kernels use (norm_rows.h), so
 // the outputs are bit for bit those of vqa_gemm + vqa_layernorm_fwd / vqa_rmsnorm_fwd.
 //
-// Instantiated, in bf16 and in e4m3, for tile configs
-//   3 (64x64, 4 stages), 4 (64x64, 2), 5 (64x64, 3), 6 (128x64, 2), 7 (64x128, 2),
-//   21 (64x64, 2 stages of 128-deep k-tiles):
+// Instantiated, in bf16 and in e4m3, for the NORM rows of VQA_GEMM_TILE_TABLE (include/vqa_hip.h):
 // what vqa_gemm_select returns on auto for a norm descriptor (3, 4; e4m3: 4), and the configs
 // the committed tuning table holds for the SAME GEMMs without a norm -- 21 for the T5 o and SGA
 // m2 / fc2 projections at D = 768 and for every e4m3 one at D = 1024, 6 for the batched SGA
@@ -39,18 +37,17 @@ int launch_norm(GemmParams& P, NormParams& Q, int batch, hipStream_t s) {
   return vqa::check_launch("vqa_gemm(norm)");
 }
 
-// tile configs with a NORM instantiation
+// the NORM rows of the tile table
 template <bool F8>
 int dispatch_norm(GemmParams& P, NormParams& Q, int batch, int config, hipStream_t s) {
-  switch (config) {
-    case 3: return launch_norm<64, 64, 4, 2, 2, BK, F8>(P, Q, batch, s);
-    case 4: return launch_norm<64, 64, 2, 2, 2, BK, F8>(P, Q, batch, s);
-    case 5: return launch_norm<64, 64, 3, 2, 2, BK, F8>(P, Q, batch, s);
-    case 6: return launch_norm<128, 64, 2, 2, 2, BK, F8>(P, Q, batch, s);
-    case 7: return launch_norm<64, 128, 2, 2, 2, BK, F8>(P, Q, batch, s);
-    case 21: return launch_norm<64, 64, 2, 2, 2, 128, F8>(P, Q, batch, s);
-    default: return vqa::fail(VQA_ERR_INVALID, "vqa_gemm(norm): tile config %d has no norm tail (3-7, 21)", config);
-  }
+  return with_tile(config, [&](auto c) {
+    constexpr Tile T = TILES[decltype(c)::value];
+    constexpr const char* why = tile_lacks(T, true, false, F8, true, false);
+    if constexpr (why != nullptr)
+      return vqa::fail(VQA_ERR_INVALID, "vqa_gemm(norm): tile config %d %s", T.id, why);
+    else
+      return launch_norm<T.bm, T.bn, T.stages, T.wm, T.wn, T.bkt, F8>(P, Q, batch, s);
+  });
 }
 
 }  // namespace

@@ -97,23 +97,45 @@ class AttnDesc(ctypes.Structure):
     ]
 
 
-# vqa_gemm tile configs (gemm.hip dispatch_tile): config -> (BM, BN, LDS stages)
-# config -> (BM, BN, stages); 1-8 run 4 waves (2x2), 9-12 run 8 waves (include/vqa_hip.h)
-GEMM_TILES = {1: (128, 128, 3), 2: (128, 64, 4), 3: (64, 64, 4), 4: (64, 64, 2), 5: (64, 64, 3), 6: (128, 64, 2),
-              7: (64, 128, 2), 8: (128, 128, 2), 9: (256, 128, 2), 10: (128, 256, 2), 11: (256, 256, 2),
-              12: (256, 128, 3), 13: (64, 192, 2), 14: (128, 192, 2), 15: (64, 192, 3), 16: (128, 192, 3),
-              17: (128, 64, 2), 18: (128, 128, 2), 19: (64, 64, 2), 20: (64, 128, 2),
-              21: (64, 64, 2), 22: (64, 128, 2), 23: (128, 64, 2), 24: (64, 128, 2), 25: (128, 128, 3),
-              26: (64, 128, 1), 27: (128, 64, 1), 28: (64, 64, 1)}
-GEMM_PATCH_ONLY = (17, 18, 19, 20, 25)   # the LDS-patch 3x3 convolution (a_conv = 2) and nothing else
-GEMM_KC_B_ONLY = (13, 14, 15, 16)        # tile configs that need a k-contiguous B operand (b_trans = 0)
-GEMM_BK128 = (21, 22, 23, 24)            # 128-deep k-tiles: no implicit im2col operand, no split-K
-GEMM_K64_ONLY = (26, 27, 28)             # one k-tile in a single-stage ring: k <= 64, no implicit im2col, no split-K
-GEMM_FP8 = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 21, 22, 23)   # tile configs with an e4m3 form (gemm_fp8.hip)
-GEMM_WAVES = {c: ((4, 2) if c in (9, 12, 25) else (2, 4) if c in (10, 11, 24) else (2, 2)) for c in GEMM_TILES}
+def gemm_tile_table():
+    """The rows of VQA_GEMM_TILE_TABLE (include/vqa_hip.h), the one list of vqa_gemm's tile configs:
+    id -> (BM, BN, LDS stages, waves_m, waves_n, k-tile depth, flag names)."""
+    txt = open(HEADER).read()
+    rows = re.findall(r"^\s*X\(" + r"\s*(\d+)\s*," * 7 + r"([^)]*)\)", txt, re.M)
+    n = int(re.search(r"#define VQA_GEMM_CONFIGS (\d+)", txt).group(1))
+    if [int(r[0]) for r in rows] != list(range(1, n + 1)):
+        raise RuntimeError(f"{HEADER}: the ids of VQA_GEMM_TILE_TABLE are not 1..VQA_GEMM_CONFIGS = {n}: "
+                           f"{[int(r[0]) for r in rows]}")
+    return {int(r[0]): tuple(map(int, r[1:7])) + (frozenset(re.findall(r"VQA_TILE_(\w+)", r[7])),) for r in rows}
 
-GEMM_NORM = (3, 4, 5, 6, 7, 21)           # tile configs with a row-norm tail (vqa_gemm_desc.norm), bf16 and e4m3
+
+def _flagged(flag):
+    return tuple(c for c, t in _TILE_TABLE.items() if flag in t[6])
+
+
+_TILE_TABLE = gemm_tile_table()
+GEMM_TILES = {c: t[:3] for c, t in _TILE_TABLE.items()}        # config -> (BM, BN, LDS stages)
+GEMM_WAVES = {c: t[3:5] for c, t in _TILE_TABLE.items()}       # config -> (waves_m, waves_n)
+GEMM_PATCH_ONLY = _flagged("PATCH")      # the LDS-patch 3x3 convolution (a_conv = 2) and nothing else
+GEMM_KC_B_ONLY = _flagged("KC_B")        # tile configs that need a k-contiguous B operand (b_trans = 0)
+GEMM_K64_ONLY = _flagged("K1")           # one k-tile in a single-stage ring: k <= 64
+GEMM_FP8 = _flagged("FP8")               # tile configs with an e4m3 form
+GEMM_NORM = _flagged("NORM")             # tile configs with a row-norm tail (vqa_gemm_desc.norm), bf16 and e4m3
+GEMM_PAIR = _flagged("PAIR")             # tile configs vqa_gemm_pair has kernels for
+GEMM_BK128 = tuple(c for c, t in _TILE_TABLE.items() if t[5] == 128)      # 128-deep k-tiles
+# derived as in the library (gemm_body.h Tile): no implicit-im2col operand; no split-K
+GEMM_PLAIN_ONLY = tuple(sorted(GEMM_BK128 + GEMM_K64_ONLY))
+GEMM_NO_SPLITK = tuple(sorted(GEMM_PLAIN_ONLY + GEMM_PATCH_ONLY))
 NORM_LAYER, NORM_RMS = 1, 2              # vqa_gemm_desc.norm
+
+
+def gemm_config_fits(cfg, d):
+    """Does vqa_gemm take tile config `cfg` for the GemmDesc `d`?  The library's eligibility check
+    (gemm.hip check_tile) over the parsed flags, split-K aside (GEMM_NO_SPLITK)."""
+    im2col = bool(d.a_conv or d.b_conv)
+    return not ((cfg in GEMM_PATCH_ONLY) != (d.a_conv == 2) or (d.norm and cfg not in GEMM_NORM)
+                or (d.fp8 and cfg not in GEMM_FP8) or (cfg in GEMM_KC_B_ONLY and d.b_trans)
+                or (cfg in GEMM_PLAIN_ONLY and im2col) or (cfg in GEMM_K64_ONLY and d.k > 64))
 
 ATTN_MFMA, ATTN_LONG, ATTN_VALU = 0, 1, 2          # vqa_attn_path
 MAX_GROUPS = 8

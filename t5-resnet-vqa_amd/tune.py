@@ -7,7 +7,6 @@ from __future__ import annotations
 import ctypes
 import json
 import os
-import re
 import sys
 
 import torch
@@ -21,7 +20,7 @@ SPLITS = (1, 2, 3, 4, 6, 8)        # split-K counts the tuner tries for small gr
 
 
 def lib_gemm_configs():
-    return int(re.search(r"#define VQA_GEMM_CONFIGS (\d+)", open(L.HEADER).read()).group(1))
+    return max(L.GEMM_TILES)
 
 
 def _gemm_key(d):
@@ -107,8 +106,8 @@ def autotune(eng, calls, reps=5, table=None, save=None, cold=False):
             if key not in cache:
                 timed.append(key)
                 best = None
-                for c1 in (3, 4, 6, 7):
-                    for c2 in (3, 4, 6, 7):
+                for c1 in L.GEMM_PAIR:
+                    for c2 in L.GEMM_PAIR:
                         d1.config, d2.config = c1, c2
                         t = time_call(c)
                         if best is None or t < best[0]:
@@ -126,18 +125,10 @@ def autotune(eng, calls, reps=5, table=None, save=None, cold=False):
             best = None
             nk = -(-d.k // 64)
             for cfg in range(1, lib_gemm_configs() + 1):
-                if (cfg in L.GEMM_KC_B_ONLY and d.b_trans) or ((cfg in L.GEMM_PATCH_ONLY) != (d.a_conv == 2)):
+                if not L.gemm_config_fits(cfg, d):
                     continue
-                if d.fp8 and cfg not in L.GEMM_FP8:
-                    continue
-                if d.norm and cfg not in L.GEMM_NORM:
-                    continue                           # tile configs with a row-norm tail
                 bm, bn, _ = L.GEMM_TILES[cfg]
                 tiles = -(-d.m // bm) * -(-d.n // bn) * max(1, d.batch)
-                if cfg in L.GEMM_BK128 and (d.a_conv or d.b_conv):
-                    continue                           # 128-deep k-tiles: plain operands only
-                if cfg in L.GEMM_K64_ONLY and (d.k > 64 or d.a_conv or d.b_conv):
-                    continue                           # one k-tile, plain operands only
                 if d.norm:                             # no split-K; the descriptor's workspace = its counters
                     d.config = cfg
                     t = time_call(c)
@@ -146,8 +137,7 @@ def autotune(eng, calls, reps=5, table=None, save=None, cold=False):
                     continue
                 for sk in SPLITS:
                     # split only grids that leave CUs idle, with >= 2 k-tiles per slice
-                    if sk > 1 and (tiles >= 512 or nk < 2 * sk or tiles > 16384 or d.a_conv == 2
-                                   or cfg in L.GEMM_BK128 or cfg in L.GEMM_K64_ONLY):
+                    if sk > 1 and (tiles >= 512 or nk < 2 * sk or tiles > 16384 or cfg in L.GEMM_NO_SPLITK):
                         continue
                     d.config = cfg
                     ops.set_splitk(d, sk)
