@@ -369,7 +369,17 @@ int vqa_colsum_partials(const float* ws, int parts, long long stride, int cols, 
  * vqa_colsum_batched then finishes any number of such reductions in ONE launch.
  * jobs: DEVICE array; job j covers blocks [first_block, first_block + ceil(cols/64))
  * (first_block cumulative, nblocks = total), each computing
- * out[c] = beta*out[c] + sum_{p < parts} ws[p*stride + c] in fixed order. */
+ * out[c] = beta*out[c] + sum_{p < parts} ws[p*stride + c] in fixed order.
+ * What a deferred call writes, and nothing else (tests/test_norm_reduce_gpu.py):
+ *   rmsnorm:   ws[p*d + c], p < vqa_norm_bwd_parts(rows): one job {ws, stride d, cols d};
+ *   layernorm: ws[(p*3 + k)*d + c], k = 0 dgamma, 1 dbeta, 2 dsum: one job per k
+ *              {ws + k*d, stride 3*d, cols d}.  dsum is only a FLAG here (non-NULL: compute the
+ *              third slot; the pointer itself is never written); with dsum == NULL the third
+ *              slot of every part is left unwritten;
+ *   colsum:    ws[p*cols + c], p < vqa_colsum_parts(rows): one job {ws, stride cols, cols}.
+ * dw / dgamma / dbeta / out stay untouched, and so does ws beyond those partial rows.  The
+ * batched reduction gives the bits of the immediate form (same part order).  first_block of
+ * job j = sum_{i < j} ceil(cols_i / 64), ascending; nblocks = that sum over all jobs. */
 typedef struct vqa_colsum_job {
   const float* ws; float* out; long long stride; int parts; int cols; float beta; int first_block;
 } vqa_colsum_job;

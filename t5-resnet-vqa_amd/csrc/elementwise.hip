@@ -470,7 +470,7 @@ extern "C" int vqa_colsum_parts(int rows) { return vqa::cdiv(rows, COLSUM_ROWS);
 
 extern "C" int vqa_colsum(const void* x, int x_bf16, int rows, int cols, long long ld, float* out, float beta,
                           float* ws, hipStream_t s) {
-  VQA_REQUIRE(x && ws && cols % 4 == 0 && ld % 4 == 0, "vqa_colsum: bad arguments");
+  VQA_REQUIRE(x && ws && rows > 0 && cols > 0 && cols % 4 == 0 && ld % 4 == 0, "vqa_colsum: bad arguments");
   const int parts = vqa::cdiv(rows, COLSUM_ROWS);
   dim3 grid(vqa::cdiv(cols, 256), parts);
   if (x_bf16)

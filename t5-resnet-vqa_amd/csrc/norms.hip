@@ -342,7 +342,8 @@ extern "C" int vqa_rmsnorm_bwd(const float* dy, const float* x, const float* rst
                                float* dx32, void* dx16, float* dw, float dw_beta, float* ws, int rows, int d,
                                const vqa_dropout* drop_dy, const vqa_dropout* drop_dx32, const vqa_dropout* drop_dx16,
                                hipStream_t s) {
-  VQA_REQUIRE(dy && x && rstd && w && ws && (dx32 || dx16) && d % 256 == 0, "vqa_rmsnorm_bwd: bad arguments");
+  VQA_REQUIRE(dy && x && rstd && w && ws && (dx32 || dx16) && rows > 0 && d % 256 == 0,
+              "vqa_rmsnorm_bwd: bad arguments");
   VQA_REQUIRE(dr_ok(drop_dy) && dr_ok(drop_dx32) && dr_ok(drop_dx16), "vqa_rmsnorm_bwd: dropout p must be in [0, 1)");
   const int parts = vqa_norm_bwd_parts(rows);
   DISPATCH_NV(d, hipLaunchKernelGGL(rmsnorm_bwd_kernel<NV>, dim3(parts), dim3(256), 0, s, dy, x, rstd, w, dres, dx32,
@@ -357,7 +358,8 @@ extern "C" int vqa_rmsnorm_bwd(const float* dy, const float* x, const float* rst
 
 extern "C" int vqa_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y32, void* y16,
                                  float* mean, float* rstd, int rows, int d, float eps, hipStream_t s) {
-  VQA_REQUIRE(x && gamma && beta && mean && rstd && (y32 || y16) && d % 256 == 0, "vqa_layernorm_fwd: bad arguments");
+  VQA_REQUIRE(x && gamma && beta && mean && rstd && (y32 || y16) && rows > 0 && d % 256 == 0,
+              "vqa_layernorm_fwd: bad arguments");
   dim3 grid(vqa::cdiv(rows, ROWS_PER_BLOCK));
   DISPATCH_NV(d, hipLaunchKernelGGL(layernorm_fwd_kernel<NV>, grid, dim3(256), 0, s, x, gamma, beta, y32,
                                     (bf16_t*)y16, mean, rstd, rows, eps));
@@ -368,7 +370,8 @@ extern "C" int vqa_layernorm_bwd(const float* dy, const float* x, const float* m
                                  const float* gamma, const float* dres, float* dx32, void* dx16, float* dgamma,
                                  float* dbeta, float* ws, int rows, int d, const vqa_dropout* drop_dx16,
                                  float* dsum, hipStream_t s) {
-  VQA_REQUIRE(dy && x && mean && rstd && gamma && ws && (dx32 || dx16) && d % 256 == 0 && !dgamma == !dbeta,
+  VQA_REQUIRE(dy && x && mean && rstd && gamma && ws && (dx32 || dx16) && rows > 0 && d % 256 == 0 &&
+                  !dgamma == !dbeta,
               "vqa_layernorm_bwd: bad arguments");
   VQA_REQUIRE(dr_ok(drop_dx16), "vqa_layernorm_bwd: dropout p must be in [0, 1)");
   const int parts = vqa_norm_bwd_parts(rows);
