@@ -622,7 +622,32 @@ int vqa_eval_rows(const vqa_eval_desc* d, hipStream_t stream);
  * no-op while PENDING == 0: a caller that defers the update (the engine applies
  * it segment by segment inside the next forward, each parameter range just
  * before its first use) clears PENDING (16 bytes at state + 8, vqa_zero) once
- * every range is applied, so the update is applied exactly once. */
+ * every range is applied, so the update is applied exactly once.
+ *
+ * Partials.  vqa_grad_sqnorm(g, n, ws, parts) writes ws[0, parts): with S = 256 x parts, float4 i
+ * of g (n / 4 of them; g 16-byte aligned, else VQA_ERR_INVALID) belongs to partial
+ * (i mod S) div 256, and each partial is the fp64 sum of the fp64 squares of its elements; n = 0
+ * gives zeros.  vqa_grad_sqnorm_final promises the same partition per range.
+ *
+ * Hyper-parameters are C floats.  beta1, beta2, eps, weight_decay and the LRs act as exactly those
+ * fp32 values: 1 - beta is formed from the float beta (1.f - 0.999f, which is 1.3e-5 below
+ * float(0.001), the constant torch adds with), and the bias corrections 1 - beta^t are formed in
+ * double from the float betas.  LR_SCALE, BC1 and BC2_SQRT hold the fp32 roundings of the double
+ * values; CLIP_COEF = fminf(1, max_norm / (GRAD_NORM + 1e-6f)) in fp32 from the stored GRAD_NORM
+ * (1 when max_norm <= 0).
+ *
+ * Non-finite norms.  An inf partial gives GRAD_NORM = inf and CLIP_COEF = 0.  A NaN partial gives
+ * GRAD_NORM = NaN and CLIP_COEF = 1 (fminf drops the NaN), where torch's clip_grad_norm_ would
+ * give a NaN coefficient: the NaN still reaches the parameters through the gradient itself, and
+ * the row-split table update below, whose identity with the dense pass rests on 0 x coef = 0 and
+ * so ASSUMES A FINITE clip coefficient, keeps holding.
+ *
+ * vqa_adamw_amsgrad / vqa_adamw_rows return VQA_ERR_INVALID, launching nothing, for n <= 0,
+ * n % 4 != 0, a group end % 4 != 0, ngroups outside [1, VQA_MAX_GROUPS], a param, grad, exp_avg,
+ * exp_avg_sq or max_exp_avg_sq that is not 16-byte aligned or a param16 that is not 8-byte aligned
+ * (vqa_adamw_rows also for rows x cols != n).  Group ends may be negative or beyond n, as in a
+ * window [lo, hi) of a larger range (pointers moved to lo, n = hi - lo, ends minus lo): the window
+ * run alone gives its elements what the whole range's run gives them, bit for bit. */
 #define VQA_MAX_GROUPS 8
 #define VQA_ST_STEP 0
 #define VQA_ST_GRAD_NORM 1

@@ -1,8 +1,7 @@
 // The AdamW-amsgrad element update (torch.optim.AdamW(amsgrad=True) with the trainer's groups,
-// faster_rcnn_vqa_trainer.py:231-267), shared by the fused optimiser pass (optim.hip) and the
-// embedding gather that reads a deferred update's result on the fly (elementwise.hip,
-// vqa_embedding_fwd_pending): both run this one function, so the gathered rows equal the rows
-// the deferred pass writes later, bit for bit.
+// faster_rcnn_vqa_trainer.py:231-267), shared by the dense pass (vqa_adamw_amsgrad) and the
+// embedding table's row-split passes (vqa_adamw_rows) of optim.hip: all run this one function,
+// so the table the row-split passes leave equals the dense pass's, bit for bit.
 #pragma once
 #include "common.h"
 
@@ -19,7 +18,10 @@ struct AdamArgs {
 inline int adam_args(const vqa_adamw_desc* d, AdamArgs& A) {
   VQA_REQUIRE(d && d->param && d->grad && d->exp_avg && d->exp_avg_sq && d->max_exp_avg_sq && d->state,
               "vqa_adamw: null argument");
-  VQA_REQUIRE(d->n % 4 == 0 && d->ngroups >= 1 && d->ngroups <= VQA_MAX_GROUPS, "vqa_adamw: bad sizes");
+  VQA_REQUIRE(d->n > 0 && d->n % 4 == 0 && d->ngroups >= 1 && d->ngroups <= VQA_MAX_GROUPS, "vqa_adamw: bad sizes");
+  VQA_REQUIRE((((uintptr_t)d->param | (uintptr_t)d->grad | (uintptr_t)d->exp_avg | (uintptr_t)d->exp_avg_sq |
+                (uintptr_t)d->max_exp_avg_sq) & 15) == 0 && ((uintptr_t)d->param16 & 7) == 0,
+              "vqa_adamw: the fp32 streams must be 16-byte aligned, param16 8-byte aligned");
   A.p = d->param; A.g = d->grad; A.m = d->exp_avg; A.v = d->exp_avg_sq; A.vm = d->max_exp_avg_sq;
   A.p16 = (bf16_t*)d->param16;
   A.n4 = d->n / 4;

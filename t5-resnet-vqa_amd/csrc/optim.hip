@@ -299,7 +299,8 @@ int grid_for(long n4) {
 }  // namespace
 
 extern "C" int vqa_grad_sqnorm(const float* g, long long n, double* ws, int parts, hipStream_t s) {
-  VQA_REQUIRE(g && ws && n % 4 == 0 && parts > 0, "vqa_grad_sqnorm: bad arguments (n %% 4 == 0)");
+  VQA_REQUIRE(g && ws && n % 4 == 0 && parts > 0 && ((uintptr_t)g & 15) == 0,
+              "vqa_grad_sqnorm: bad arguments (n %% 4 == 0, g 16-byte aligned)");
   hipLaunchKernelGGL(sqnorm_kernel, dim3(parts), dim3(256), 0, s, g, (long)(n / 4), ws);
   return vqa::check_launch("vqa_grad_sqnorm");
 }
