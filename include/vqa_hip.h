@@ -237,9 +237,22 @@ long long vqa_gemm_workspace_bytes(const vqa_gemm_desc* d);
 int vqa_gemm_pair(const vqa_gemm_desc* dx, const vqa_gemm_desc* dw, hipStream_t stream);
 
 /* ------------------------------------------------------------- attention ---
- * Multi-head attention core for Lq, Lk <= 64 (one workgroup per (b, head)):
+ * Multi-head attention core:
  *   S = scale * Q K^T (+ bias[h,i,j]) (+ finfo(f32).min where key_mask[b,j]==0)
  *   P = softmax_j(S), O = P V.
+ * Three kernel sets (vqa_attn_path says which one a descriptor gets):
+ *   MFMA  lq <= 32, lk <= 160, dh 64 / 96 / 128 (a key mask only with lk <= 64), forward and
+ *         backward, one wave per (b, head);
+ *   long  forward only, any lq, lk <= 1024, dh 64 / 96, no p / bias / mask / dropout (below);
+ *   VALU  every other shape with lq, lk <= 64 and dh % 8 == 0, one workgroup per (b, head) with
+ *         everything in LDS: the forward needs 4 ((lq + 2 lk)(dh/2 + 1) + lq (lk + 1)) bytes, the
+ *         backward 4 ((2 lq + 2 lk)(dh/2 + 1) + 2 lq (lk + 1)), each at most 65,536 (64 x 64 x 64
+ *         fits the forward, not the backward; 63 x 63 x 64 fits both).  q / k / v / dout must be
+ *         16-byte aligned, o / dq / dk / dv 4-byte aligned with even row strides.
+ * Anything else is VQA_ERR_INVALID with nothing launched.
+ * A masked pair takes ONE finfo.min, as HF's combined extended mask has it: where the bias is
+ * already <= finfo.min / 2 (a causal pair) the key mask adds nothing, so a fully masked row is
+ * the uniform 1 / lk and never -inf - -inf.
  * Replaces MHAtt.att (multi_head_vision_text_attn.py:73-86; scale 1/sqrt(96),
  * 8 heads, no mask) and T5 eager attention (TF modeling_t5.py:144-173; scale 1,
  * 12 heads, relative bias, key mask).  Element (b, i, h, e) of Q lives at
@@ -252,7 +265,10 @@ int vqa_gemm_pair(const vqa_gemm_desc* dx, const vqa_gemm_desc* dw, hipStream_t 
  * p keeps the pre-dropout P and the backward regenerates the mask.
  * Long forward (lq > 32 or lk > 64, up to lk = 1024; dh 64 / 96; no p, bias, mask or
  * dropout): ViTSelfAttention of BASELINE config 4 (vit_vqa_model.py:183-186, frozen,
- * no_grad), an online-softmax MFMA kernel; there is no long backward.
+ * no_grad), an online-softmax MFMA kernel; there is no long backward.  An evaluation
+ * forward of an MFMA shape with lk > 64 that passes p == NULL (and no bias / mask / active
+ * dropout) therefore runs the long kernel, not the MFMA one: the same O within bf16 rounding,
+ * not the same bits.
  * Causal T5 decoder self-attention (vit_vqa_model.py:199-205): the bias rows carry
  * finfo.min where j > i (vqa_t5_relbias_fwd with bucket < 0). */
 typedef struct vqa_attn_desc {
@@ -292,7 +308,8 @@ int vqa_attn_bwd(const vqa_attn_desc* d, hipStream_t stream);
 #define VQA_ATTN_VALU 2
 int vqa_attn_path(const vqa_attn_desc* d, int backward);
 /* The attention probabilities alone, d->p = [batch, heads, lq, lk] fp32:
- * softmax_j(scale q_i.k_j (+ bias) (+ finfo.min at masked keys)) for any lq, lk (dh <= 1024):
+ * softmax_j(scale q_i.k_j (+ bias) (+ finfo.min at masked keys)) for any lq, lk (dh <= 1024),
+ * with the one-finfo.min rule of vqa_attn_fwd (no second one where the bias is <= finfo.min / 2):
  * HF ViTModel(output_attentions=True), the `attentions` that VitVQAModel.generate_answers
  * returns (model/vit_vqa_model.py:238-240, 285-290).  Eval-time readout; o / v / dropout unused. */
 int vqa_attn_probs(const vqa_attn_desc* d, hipStream_t stream);

@@ -1,5 +1,6 @@
 // Fused multi-head attention core, forward and backward, for the two short
-// attention shapes of the step (Lq, Lk <= 64):
+// attention shapes of the step (Lq, Lk <= 64; the scalar VALU kernels, the fall-back for
+// every shape the MFMA kernels of attention_mfma.hip do not take):
 //   SGA  MHAtt.att   softmax(QK^T/sqrt(96)) V, 8 heads x 96     multi_head_vision_text_attn.py:73-86
 //   T5   attention   softmax(QK^T + relbias + mask) V, 12 x 64  TF/models/t5/modeling_t5.py:144-173
 // One workgroup per (batch, head).  Q/K/V/dO are staged in LDS as packed bf16
@@ -182,8 +183,19 @@ size_t bwd_smem(int lq, int lk, int dh) {
   return 4ul * ((2 * lq + 2 * lk) * (dh / 2 + 1) + 2 * lq * (lk + 1));
 }
 
-int fill(AttnP& P, const vqa_attn_desc* d) {
+int fill(AttnP& P, const vqa_attn_desc* d, bool bwd) {
   VQA_REQUIRE(d && d->q && d->k && d->v, "attention: null q/k/v");
+  auto al = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+  // stage() reads rows as uint4; the outputs are stored as packed bf16 pairs (uint32_t)
+  VQA_REQUIRE(al(d->q, 16) && al(d->k, 16) && al(d->v, 16), "attention: q / k / v must be 16-byte aligned");
+  if (bwd) {
+    VQA_REQUIRE(al(d->dout, 16), "vqa_attn_bwd: dO must be 16-byte aligned");
+    VQA_REQUIRE(al(d->dq, 4) && al(d->dk, 4) && al(d->dv, 4), "vqa_attn_bwd: dQ / dK / dV must be 4-byte aligned");
+    VQA_REQUIRE(d->lddq % 2 == 0 && d->lddk % 2 == 0 && d->lddv % 2 == 0,
+                "vqa_attn_bwd: dQ / dK / dV strides must be even");
+  } else {
+    VQA_REQUIRE(al(d->o, 4) && d->ldo % 2 == 0, "vqa_attn_fwd: O must be 4-byte aligned with an even stride");
+  }
   VQA_REQUIRE(d->lq > 0 && d->lk > 0 && d->lq <= 64 && d->lk <= 64, "attention: lq, lk must be in [1, 64]");
   VQA_REQUIRE(d->dh % 8 == 0 && d->dh <= 256, "attention: head dim must be a multiple of 8");
   VQA_REQUIRE(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldv % 8 == 0, "attention: strides must be multiples of 8");
@@ -223,8 +235,10 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(AttnP P, int pairs) {
       acc = fmaf(qs[c], kv.x, fmaf(qs[c + 1], kv.y, acc));
     }
     float v = acc * P.scale;
-    if (P.bias) v += P.bias[((long)hh * P.lq + i) * P.lk + j];
-    if (P.mask && P.mask[(long)b * P.lk + j] == 0) v += MASK_MIN;
+    const float bv = P.bias ? P.bias[((long)hh * P.lq + i) * P.lk + j] : 0.f;
+    v += bv;
+    if (P.mask && P.mask[(long)b * P.lk + j] == 0 && !(bv <= 0.5f * MASK_MIN))
+      v += MASK_MIN;                                   // one finfo.min per masked pair, as attn_fwd_kernel
     prow[j] = v;
     mx = fmaxf(mx, v);
   }
@@ -273,7 +287,7 @@ extern "C" int vqa_attn_fwd(const vqa_attn_desc* d, hipStream_t s) {
               "attention: groups > 1 needs the MFMA shapes and no bias / key mask");
   if (vqa_attn_mfma_ok(d)) return vqa_attn_fwd_mfma(d, s);        // the step's shapes (lk <= 160)
   AttnP P;
-  if (int rc = fill(P, d)) return rc;
+  if (int rc = fill(P, d, false)) return rc;
   const size_t sm = fwd_smem(d->lq, d->lk, d->dh);
   VQA_REQUIRE(sm <= 65536, "vqa_attn_fwd: shape needs %zu B of LDS (> 64 KiB)", sm);
   hipLaunchKernelGGL(attn_fwd_kernel, dim3(d->batch * d->heads), dim3(256), sm, s, P);
@@ -291,7 +305,7 @@ extern "C" int vqa_attn_bwd(const vqa_attn_desc* d, hipStream_t s) {
               "attention: groups > 1 needs the MFMA shapes and no bias / key mask");
   if (vqa_attn_mfma_ok(d)) return vqa_attn_bwd_mfma(d, s);        // lk <= 160
   AttnP P;
-  if (int rc = fill(P, d)) return rc;
+  if (int rc = fill(P, d, true)) return rc;
   const size_t sm = bwd_smem(d->lq, d->lk, d->dh);
   VQA_REQUIRE(sm <= 65536, "vqa_attn_bwd: shape needs %zu B of LDS (> 64 KiB)", sm);
   hipLaunchKernelGGL(attn_bwd_kernel, dim3(d->batch * d->heads), dim3(256), sm, s, P);
