@@ -81,7 +81,17 @@ int vqa_dropout_mask(const vqa_dropout* d, float* out, long long n, hipStream_t 
  *   With res, relu acts after the residual (ResNet); relu with dropout needs no res.
  *   `relu` is the epilogue activation: 0 none, 1 ReLU, 2 GELU (erf form), 3 tanh;
  *   GELU / tanh take no dropout and no mask16 (ViT intermediate / pooler, config 4).
- * batch > 1 offsets a, b, c32, c16 by their strides and res/mask by stride_res. */
+ *   res = res32 + res16: both add when both are given (they share ldres and stride_res).  c32 == res32
+ *   (with ldres == ldc32) is allowed: each element's residual is read before that element is stored.
+ *   beta never enters c16: c16 = RNE-bf16(v) of the v before beta*c32, the same bits with and without beta.
+ *   GELU / tanh run ONE tile (64 x 128, 2 stages) whatever config is asked for: any config outside PATCH
+ *   is accepted and gives the same bits.  They exist for k-contiguous A and B alone: with a_trans,
+ *   b_trans, a_conv (1 or 2), b_conv, split-K or fp8 the call is VQA_ERR_INVALID, never a silent ReLU.
+ * batch > 1 offsets a, b, c32, c16 by their strides and res32, res16 AND mask16 by stride_res (the mask has
+ *   no stride of its own).
+ * b_conv needs k and gb.n * gb.oh * gb.ow below 2^24 (the loader splits k with a float reciprocal that is
+ *   exact there): VQA_ERR_INVALID beyond.  A refused call writes nothing.
+ * tests/gemm_ref.py restates this contract in fp64; tests/test_gemm_parity_gpu.py holds every kernel to it. */
 typedef struct vqa_conv_geom {
   int n, h, w, c;          /* NHWC input */
   int oh, ow;              /* output spatial size */
@@ -126,9 +136,12 @@ typedef struct vqa_gemm_desc {
    * (a_trans = b_trans = 0), both row-wise quantised by vqa_quant_rows_fp8; the accumulator
    * is scaled by scale_a[z*stride_scale_a + row] * scale_b[z*stride_scale_b + col] before the
    * epilogue (bias / residual / ReLU / dropout as usual).  k and lda / ldb multiples of 16,
-   * n % 4 == 0, no conv operand, no GELU / tanh.  Products of e4m3 values are
-   * exact in fp32, so the result differs from an fp32 GEMM of the dequantised operands only
-   * by accumulation order. */
+   * n % 4 == 0, no conv operand, no GELU / tanh.  Products of e4m3 values are exact in fp32, but
+   * the 64-deep MFMA does not sum them exactly: within a group of neighbouring k it aligns the
+   * products to the largest one and drops what lies 2^-13 below it (measured: 256 * 1 + 2^-6 gives
+   * 256).  Against an fp64 GEMM of the dequantised operands the result errs by up to 2.4e-5 of
+   * sum_k |a b| at k = 16 and less at larger k (tests/test_gemm_parity_gpu.py), where the bf16
+   * kernels stay below 2e-7. */
   int fp8;
   const float* scale_a;
   const float* scale_b;
@@ -233,7 +246,8 @@ long long vqa_gemm_workspace_bytes(const vqa_gemm_desc* d);
  * conv.  Each keeps its own epilogue and tile config (the configs with the PAIR flag of
  * VQA_GEMM_TILE_TABLE; others map to 4).  Any other pair of descriptors runs as two vqa_gemm
  * calls.  A descriptor with norm != 0 is rejected (VQA_ERR_INVALID): the paired kernel has no
- * norm tail. */
+ * norm tail.  A (dX, dW) pair with relu >= 2 in either descriptor is rejected too, before either half
+ * is launched: the paired kernel has no GELU / tanh epilogue, and vqa_gemm takes neither layout with one. */
 int vqa_gemm_pair(const vqa_gemm_desc* dx, const vqa_gemm_desc* dw, hipStream_t stream);
 
 /* ------------------------------------------------------------- attention ---

@@ -223,6 +223,7 @@ static int conv_patch_dispatch(GemmParams& P, int config, hipStream_t s) {
               "vqa_gemm(a_conv=2): a 3x3 / stride-1 / pad-1 convolution is required");
   VQA_REQUIRE(g.c % 64 == 0 && P.k == 9 * g.c && P.m == g.n * g.h * g.w, "vqa_gemm(a_conv=2): C %% 64, K = 9C, M = NHW");
   VQA_REQUIRE(P.splitk <= 1 && P.alpha == 1.f, "vqa_gemm(a_conv=2): no split-K, alpha = 1");
+  VQA_REQUIRE(P.relu <= 1, "vqa_gemm(a_conv=2): ReLU at most (the patch kernel has no GELU / tanh epilogue)");
   VQA_REQUIRE(config >= 1 && config <= VQA_GEMM_CONFIGS && TILES[config].has(VQA_TILE_PATCH),
               "vqa_gemm(a_conv=2): tile config %d is not an LDS-patch config", config);
   const Tile& t = TILES[config];

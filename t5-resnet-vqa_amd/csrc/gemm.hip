@@ -173,6 +173,9 @@ static int prepare(const vqa_gemm_desc* d, GemmParams& P) {
   VQA_REQUIRE(!(d->b_conv && !d->b_trans), "vqa_gemm: b_conv needs b_trans=1");
   VQA_REQUIRE(!d->a_conv || d->ga.c % 8 == 0, "vqa_gemm: conv input channels must be a multiple of 8");
   VQA_REQUIRE(!d->b_conv || d->gb.c % 8 == 0, "vqa_gemm: conv input channels must be a multiple of 8");
+  // the b_conv loader splits k = (img, oh, ow) with fdiv, exact below 2^24 (gemm_common.h)
+  VQA_REQUIRE(!d->b_conv || (d->k < (1 << 24) && (long long)d->gb.n * d->gb.oh * d->gb.ow < (1 << 24)),
+              "vqa_gemm: b_conv needs k and n * oh * ow below 2^24");
   VQA_REQUIRE(d->batch >= 1, "vqa_gemm: batch must be >= 1");
   VQA_REQUIRE(d->config >= 0 && d->config <= VQA_GEMM_CONFIGS, "vqa_gemm: config must be 0..%d", VQA_GEMM_CONFIGS);
   VQA_REQUIRE(d->drop.p >= 0.f && d->drop.p < 1.f, "vqa_gemm: dropout p must be in [0, 1)");
@@ -356,6 +359,10 @@ extern "C" int vqa_gemm_pair(const vqa_gemm_desc* dx, const vqa_gemm_desc* dw, h
   const bool shape_ok = !dx->a_trans && dx->b_trans && !dx->a_conv && !dx->b_conv && dx->batch == 1 &&
                         dw->a_trans && dw->b_trans && !dw->a_conv && !dw->b_conv && dw->batch == 1 &&
                         P1.splitk == 1 && P2.splitk == 1;
+  // the paired kernel has no GELU / tanh epilogue (it would run them as ReLU), and vqa_gemm takes neither
+  // layout with one: refused here, before either half is launched
+  VQA_REQUIRE(!shape_ok || (dx->relu <= 1 && dw->relu <= 1),
+              "vqa_gemm_pair: GELU / tanh epilogues need k-contiguous A and B (vqa_gemm)");
   if (!shape_ok) {                                       // not a (dX, dW) pair: run them one after the other
     if (int rc = vqa_gemm(dx, stream)) return rc;
     return vqa_gemm(dw, stream);

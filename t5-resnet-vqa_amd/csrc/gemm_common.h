@@ -82,7 +82,8 @@ __device__ __forceinline__ int mn_off(int kr, int ch) {
   return kr * (ROWLEN * 2) + ((ch ^ mn_swz<ROWLEN>(kr)) << 4);
 }
 
-// a / d for 0 <= a < 2^22 via a float reciprocal + one-step correction (no integer division)
+// a / d for 0 <= a < 2^24 via a float reciprocal + one-step correction (no integer division;
+// tests/test_gemm_ref_cpu.py sweeps every a for the divisors in use, prepare() holds b_conv to the range)
 __device__ __forceinline__ int fdiv(int a, int d, float inv) {
   int q = (int)((float)a * inv);
   q -= (q * d > a) ? 1 : 0;
