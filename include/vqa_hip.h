@@ -739,6 +739,23 @@ int vqa_embed_mark(const long long* ids, int n, int rows, int* mark, const float
 int vqa_adamw_rows(const vqa_adamw_desc* d, const int* mark, int rows, int cols, int touched, int warmup, int total,
                    hipStream_t stream);
 
+/* ---------------------------------------------------- gradient accumulation ---
+ * k micro-batches of one global batch per optimizer step (new symbols; the ABI version is
+ * unchanged).  Device state: micro = one int32, the micro-batches accumulated so far in this
+ * optimizer step; acc_loss = one double.  The counter is read on the device, so one captured
+ * micro-batch graph serves every position of the step.
+ * vqa_grad_accumulate: micro[0] == 0: acc[i] = g[i] (a dense copy); else acc[i] = acc[i] + g[i],
+ *   one fp32 add per element, no scale, no atomics; g and micro are only read.  n <= 0,
+ *   n % 4 != 0 or an acc / g that is not 16-byte aligned is VQA_ERR_INVALID, nothing launched.
+ * vqa_accum_advance (one workgroup): logp_all[micro * batch * answers ...] = the batch * answers
+ *   floats of logp; acc_loss = (micro == 0 ? 0 : acc_loss) + (double)loss[0]; then micro += 1.
+ *   A counter outside [0, k) writes nothing.
+ * vqa_accum_finish: loss[0] = (float)(acc_loss / k), micro = 0. */
+int vqa_grad_accumulate(float* acc, const float* g, long long n, const int* micro, hipStream_t stream);
+int vqa_accum_advance(const float* logp, float* logp_all, int batch, int answers, int k, const float* loss,
+                      double* acc_loss, int* micro, hipStream_t stream);
+int vqa_accum_finish(float* loss, const double* acc_loss, int* micro, int k, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

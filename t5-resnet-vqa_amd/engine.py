@@ -67,6 +67,18 @@ def stem_s2d_weight(wf):
     return np.concatenate([w, np.zeros((co, 4, 4, 16 - 4 * ci), np.float32)], 3)
 
 
+def accum_spans(rows, batch, k):
+    """The (lo, hi) row spans of the k micro-batches of a `rows`-row global batch, `batch` rows
+    planned per micro-batch: a contiguous split, full micro-batches first, then the remainder,
+    then empty ones (lo == hi).  1 <= rows <= k x batch."""
+    rows, batch, k = int(rows), int(batch), int(k)
+    if batch < 1 or k < 1:
+        raise ValueError(f"accum_spans: batch={batch} and k={k} must be >= 1")
+    if not 1 <= rows <= k * batch:
+        raise ValueError(f"global batch of {rows} rows: {k} micro-batches of {batch} rows take 1..{k * batch}")
+    return [(min(j * batch, rows), min((j + 1) * batch, rows)) for j in range(k)]
+
+
 class VQAEngine(EngineBase):
     def __init__(self, state_dict, vision="resnet50", batch=64, seq_len=32, image_size=224, device="cuda:0",
                  warmup=10, total=100, num_blocks=3, answer_spaces=170, grad_scale=1.0, max_norm=1.0,
@@ -167,6 +179,9 @@ class VQAEngine(EngineBase):
         self.allow_empty_rows = False     # use_global_rows (DP): a rank may get 0 rows
         self._img_rows_next = None        # pipelined: rows of the images whose features the next batch uses
         self.count_call = None
+        # gradient accumulation (use_accumulation): micro-batches per optimizer step, the calls that
+        # end a micro-batch (accumulate, advance), the launch that ends the step, rows of the last one
+        self.accum, self.accum_calls, self.accum_finish, self.accum_rows = 1, [], None, 0
 
     @classmethod
     def from_state_dict(cls, sd, **kw):
@@ -601,11 +616,12 @@ class VQAEngine(EngineBase):
         a = self._sq_split[1] if self._sq_split is not None else e0
         assert a % 4 == 0 and e0 % 4 == 0 and (n - e0) % 4 == 0 and a <= e0
         K = self.SQ_PARTS
-        self._call(o, "vqa_grad_sqnorm", self.G32, a, self.WS_SQ, K)
-        self._call(o, "vqa_grad_sqnorm", ops.addr(self.G32, a), e0 - a, ops.addr(self.WS_SQ, K), K,
-                   extra=[self.G32, self.WS_SQ])
-        self._call(o, "vqa_grad_sqnorm", ops.addr(self.G32, e0), n - e0, ops.addr(self.WS_SQ, 2 * K), K,
-                   extra=[self.G32, self.WS_SQ])
+        G = self.G_OPT                    # G32, or the accumulator (use_accumulation)
+        self._call(o, "vqa_grad_sqnorm", G, a, self.WS_SQ, K)
+        self._call(o, "vqa_grad_sqnorm", ops.addr(G, a), e0 - a, ops.addr(self.WS_SQ, K), K,
+                   extra=[G, self.WS_SQ])
+        self._call(o, "vqa_grad_sqnorm", ops.addr(G, e0), n - e0, ops.addr(self.WS_SQ, 2 * K), K,
+                   extra=[G, self.WS_SQ])
         self._call(o, "vqa_optim_finalize", self.WS_SQ, 3 * K, float(self.grad_scale), float(self.max_norm),
                    int(self.warmup), int(self.total), float(self.betas[0]), float(self.betas[1]), self.opt_state)
         self._adam_desc = self._adam_desc_full()
@@ -707,11 +723,11 @@ class VQAEngine(EngineBase):
             emb = lay["t5.embed"]
             lead = emb.offset - e0
             assert lead >= 0 and lead % 4 == 0 and emb.numel == S.T5_VOCAB * self.D and self.D % 4 == 0
-            fin = ops.Call("vqa_grad_sqnorm_final", ops.addr(self.G32, a), e0 - a, ops.addr(self.G32, e0), n - e0,
+            fin = ops.Call("vqa_grad_sqnorm_final", ops.addr(G, a), e0 - a, ops.addr(G, e0), n - e0,
                            self.WS_SQ.data_ptr(), K, 3 * K, self.EMB_MARK.data_ptr(), lead, self.D,
                            self.SQ_CNT.data_ptr(), float(self.grad_scale), float(self.max_norm), int(self.warmup),
                            int(self.total), float(self.betas[0]), float(self.betas[1]), self.opt_state.data_ptr(),
-                           keep=(self.G32[a:], self.WS_SQ, self.EMB_MARK, self.SQ_CNT, self.opt_state))
+                           keep=(G[a:], self.WS_SQ, self.EMB_MARK, self.SQ_CNT, self.opt_state))
             assert [c.name for c in self.tail_calls[:2]] == ["vqa_grad_sqnorm", "vqa_optim_finalize"]
             self.tail_calls = [fin] + self.tail_calls[2:]
             ids, dh, dtab, _, _, _, ws = self.emb_call.args
@@ -770,7 +786,10 @@ class VQAEngine(EngineBase):
 
     def prime(self, images):
         """Pipelined engines: compute the layer4 features of the first batch's images, so
-        that the first train_step has them (later steps produce their successor's)."""
+        that the first train_step has them (later steps produce their successor's).
+        Accumulating engines (use_accumulation): `images` are the first B rows of the first global
+        batch; inside accum_step micro-batch j's next images are micro-batch j + 1's, and the last
+        micro-batch takes the caller's `next_images` = the first B rows of the NEXT global batch."""
         assert self.pipeline, "prime() is for pipelined engines"
         ni = batch_rows({"image_tensors": images}, "image_tensors", self.B, self.allow_empty_rows)
         load_rows(self.IMG, images, ni)
@@ -800,6 +819,122 @@ class VQAEngine(EngineBase):
         self.allow_empty_rows = True
         self.graph = None
 
+    # ------------------------------------------------------------------ gradient accumulation
+    def use_accumulation(self, k):
+        """One optimizer step = k micro-batches of the planned B rows (accum_step): the global batch
+        of up to k x B rows trains like one engine planned for k x B rows -- data parallelism laid
+        out in time.  Call it before the first capture.  k = 1 does nothing at all.  For k > 1:
+          * GACC (fp32, the arena's size) and LOGP_ALL [k B, A] are allocated, and 16 bytes of
+            device state ACC = {double loss sum, int32 micro-batches done};
+          * the head backward takes the global-rows form of use_global_rows(k): ROWTOT is the valid
+            rows of the whole global batch, counted once per optimizer step from TGT_ALL (one
+            vqa_count_targets launch, hence k x B <= 1024), so the k gradients summed and scaled by
+            1/k are the global batch's NLL mean however its rows fall into micro-batches (an empty
+            micro-batch gives a zero gradient and loss share 0);
+          * the optimizer is re-planned over GACC with grad_scale / k (one plan: squared norms,
+            finalize, every AdamW range and the row-split table update, flush_optimizer's ranges).
+        The step is k replays of ONE micro-batch graph -- forward, backward without the tail,
+        vqa_embed_mark of its ids, then on the main stream vqa_grad_accumulate(GACC, G32) and
+        vqa_accum_advance; the device counter makes the first replay copy and the others add --
+        and one finish graph: the untouched table rows' update, the squared norms of GACC, finalize,
+        the rel-bias range and the touched rows, vqa_accum_finish; the other AdamW ranges stay
+        deferred into the next step's first forward (they are no-ops in micro-batches 2..k:
+        VQA_ST_PENDING is clear by then)."""
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"use_accumulation: k={k} must be >= 1")
+        if self.accum != 1 or k == 1:
+            if k != self.accum:
+                raise ValueError(f"use_accumulation: already set for k={self.accum}")
+            return
+        if self.fp8:
+            raise ValueError("use_accumulation: fp8 engines do not accumulate")
+        if k * self.B > 1024:
+            raise ValueError(f"use_accumulation: k x batch = {k * self.B} > 1024 rows (vqa_count_targets)")
+        if self.allreduce is not None or self.count_call is not None or self.res_external:
+            raise ValueError("use_accumulation: not together with data parallel or an external ResNet stream")
+        with torch.cuda.device(self.dev):
+            self.GACC = self._t(self.lay.total, zero=True)
+            self.LOGP_ALL = self._t((k * self.B, self.A), zero=True)
+            self.TGT_ALL = torch.full((k * self.B,), IGNORE_INDEX, dtype=I64, device=self.dev)
+            self.ACC = self._t(4, torch.int32, zero=True)
+        self.use_global_rows(k)
+        self.count_call = ops.Call("vqa_count_targets", ops.addr(self.TGT_ALL), k * self.B, ops.addr(self.ROWTOT),
+                                   keep=(self.TGT_ALL, self.ROWTOT))
+        loss_sum, micro = ops.addr(self.ACC), ops.addr(self.ACC, 2)
+        self.accum_calls = [
+            ops.Call("vqa_grad_accumulate", ops.addr(self.GACC), ops.addr(self.G32), self.lay.total, micro,
+                     keep=(self.GACC, self.G32, self.ACC)),
+            ops.Call("vqa_accum_advance", ops.addr(self.LOGP), ops.addr(self.LOGP_ALL), self.B, self.A, k,
+                     ops.addr(self.LOSS), loss_sum, micro, keep=(self.LOGP, self.LOGP_ALL, self.LOSS, self.ACC))]
+        self.accum_finish = ops.Call("vqa_accum_finish", ops.addr(self.LOSS), loss_sum, micro, k,
+                                     keep=(self.LOSS, self.ACC))
+        self.accum = k
+        self.set_grad_scale(self.grad_scale / k)          # re-plans over GACC (G_OPT), drops the graph
+
+    def _finish_calls(self):
+        """The finish graph of an accumulated step, the dense tail over GACC in the shape of
+        tail_calls_unfused: the untouched table rows (before finalize; the marks are the union of
+        the k micro-batches', all stamped with the one step counter), the squared-norm partials,
+        finalize, the rel-bias range and the touched rows -- without defer_optimizer the whole
+        AdamW pass -- then vqa_accum_finish."""
+        return self.emb_pre[1:] + self.opt_calls[:2] + self.tail_calls_unfused + [self.accum_finish]
+
+    def _micro_backward(self):
+        """A micro-batch's backward: no tail.  The untouched-rows pass and the squared-norm overlap
+        belong to the finish graph (here they would update rows early and sum G32); the ids are
+        marked per micro-batch.  run_backward_streams ends with `side` and `wside` joined into the
+        main stream, and the previous step's deferred AdamW ranges, which read GACC, were issued
+        on the main stream by this micro-batch's forward: the accumulate, which overwrites GACC in
+        micro-batch 0, follows all of them in stream order."""
+        if self.embed_split:
+            self._run(self.emb_pre[:1])
+        self.run_backward_streams()
+        self._run(self.accum_calls)
+
+    def accum_step(self, batch, next_images=None, use_graph=True, on_micro=None):
+        """One optimizer step over a global batch of 1 .. k x B rows (use_accumulation(k), k > 1):
+        the rows split contiguously (accum_spans), all k micro-batches run, then the finish graph.
+        Afterwards LOSS is the global batch's mean NLL, LOGP_ALL[:rows] its log-probs and
+        last_grad_norm() the norm of its gradient.  use_graph=False issues the same calls without
+        capture.  on_micro(j) is called after micro-batch j has been issued (tests).
+        Pipelined engines: micro-batch j's next images are micro-batch j + 1's rows of
+        batch["image_tensors"]; the last micro-batch takes `next_images`, the FIRST B rows of the
+        next global batch (prime() takes the first B rows of the first one)."""
+        k, B = self.accum, self.B
+        if k == 1:
+            raise RuntimeError("accum_step: call use_accumulation(k) with k > 1 first")
+        tgt = batch.get("annotation_ids")
+        if tgt is None:
+            raise ValueError("accum_step: the batch has no annotation_ids")
+        n = int(torch.as_tensor(batch["question_input_ids"]).shape[0])
+        spans = accum_spans(n, B, k)
+        load_rows(self.TGT_ALL, tgt, n, fill=IGNORE_INDEX)
+        self._run([self.count_call])                       # ROWTOT: the valid rows of all k x B
+        for j, (lo, hi) in enumerate(spans):
+            sub = {key: batch[key][lo:hi] for key in ("question_input_ids", "question_attention_masks",
+                                                      "image_tensors", "annotation_ids") if batch.get(key) is not None}
+            if self.pipeline:
+                a, b = spans[j + 1] if j + 1 < k else (0, 0)
+                self.load_batch(sub, next_images=batch["image_tensors"][a:b] if j + 1 < k else next_images)
+            else:
+                self.load_batch(sub)
+            if use_graph and self.graph is None:
+                self.capture()
+            if not use_graph:
+                self._step_pipelined() if self.pipeline else self._run_step_streams()
+            else:
+                if self.pipeline and self.res_order == "root":
+                    self.copy_f4(L.stream_handle(torch.cuda.current_stream(self.dev)))
+                self.graph[0].replay()
+            if on_micro is not None:
+                on_micro(j)
+        if use_graph:
+            self.graph[1].replay()
+        else:
+            self._run(self._finish_calls())
+        self.accum_rows = n
+
     def forward(self):
         self.flush_optimizer()                          # the previous step's deferred update, then the forward
         super().forward()
@@ -817,7 +952,11 @@ class VQAEngine(EngineBase):
             self.run_backward_streams()
 
     def _backward_and_tail(self):
-        """The backward and optimizer tail of a full stream / graph step."""
+        """The backward and optimizer tail of a full stream / graph step (an accumulating engine:
+        the micro-batch's backward, accumulate and advance; the tail is the finish graph's)."""
+        if self.accum > 1:
+            self._micro_backward()
+            return
         self.run_backward_streams(sq_overlap=True, sorted_scatter=self.fused_tail)
         self._run(self.tail_calls)
 
@@ -1100,6 +1239,8 @@ class VQAEngine(EngineBase):
 
     def train_step(self):
         """zero_grad -> forward -> backward -> (all-reduce) -> clip -> AdamW -> sched, all on-device."""
+        if self.accum > 1:
+            raise RuntimeError("this engine accumulates micro-batches (use_accumulation): drive it with accum_step")
         if self.graph is not None and self.res_external:
             self._res_external_step()
             return
@@ -1148,6 +1289,20 @@ class VQAEngine(EngineBase):
         self.graph = parts
 
     def _capture_parts(self, s):
+        if self.accum > 1:
+            # graph(micro-batch) x k -> graph(finish): the device counter lets one micro-batch
+            # graph serve every position.  Capture runs neither: GACC and ACC stay as they are
+            # (the warm-up above is a forward and a backward, no accumulate, no advance)
+            assert self.allreduce is None and not self.res_external
+            gm, gf = self._new_graph(), self._new_graph()
+            with torch.cuda.graph(gm, stream=s):
+                if self.pipeline:
+                    self._step_pipelined()
+                else:
+                    self._run_step_streams()
+            with torch.cuda.graph(gf, stream=s):
+                self._run(self._finish_calls())
+            return [gm, gf]
         if self.allreduce is None:
             g = self._new_graph()
             with torch.cuda.graph(g, stream=s):
@@ -1207,8 +1362,19 @@ class VQAEngine(EngineBase):
     def loss(self):
         return self.LOSS
 
-    def segment_grad(self, name):
-        return self.g32[name]
+    def segment_grad(self, name, accumulated=False):
+        """Segment `name`'s gradient view: of G32 (the last micro-batch's), or with `accumulated`
+        of GACC (the global batch's sum, before the 1/k of the update)."""
+        if not accumulated:
+            return self.g32[name]
+        if self.GACC is None:
+            raise RuntimeError("segment_grad(accumulated=True): this engine does not accumulate (use_accumulation)")
+        s = self.lay[name]
+        return self.GACC[s.offset:s.offset + s.numel].view(s.shape)
+
+    def accum_log_probs(self):
+        """The log-probs of the last accum_step's global batch, [rows, A]."""
+        return self.LOGP_ALL[:self.accum_rows]
 
     def refresh_shadow(self):
         super().refresh_shadow()

@@ -195,6 +195,7 @@ class EngineBase:
         self._keep_graph = False          # capture(keep_graph=True): the hipGraph_t of each part is kept
         self._scratch = None              # split-K workspace used while autotuning
         self._jobs = []                   # column-sum reductions queued by _defer until _flush
+        self.GACC = None                  # gradient accumulator the optimizer plan reads instead of G32 (G_OPT)
 
     # ------------------------------------------------------------------ hooks
     def _model_specs(self):
@@ -416,10 +417,16 @@ class EngineBase:
             c(s)
 
     # ------------------------------------------------------------------ AdamW descriptors
+    @property
+    def G_OPT(self):
+        """The gradient arena the optimizer plan reads (squared norms, AdamW descriptors): G32, or
+        the accumulator of an engine that accumulates micro-batches (VQAEngine.use_accumulation)."""
+        return self.G32 if self.GACC is None else self.GACC
+
     def _adam_desc_full(self):
         """The AdamW-amsgrad descriptor of the whole flat arena."""
         d = L.AdamWDesc()
-        d.param, d.grad = self.P32.data_ptr(), self.G32.data_ptr()
+        d.param, d.grad = self.P32.data_ptr(), self.G_OPT.data_ptr()
         d.exp_avg, d.exp_avg_sq, d.max_exp_avg_sq = self.M.data_ptr(), self.V.data_ptr(), self.VMAX.data_ptr()
         d.param16 = self.P16.data_ptr()
         d.n = self.lay.total
@@ -438,7 +445,7 @@ class EngineBase:
         d = self._adam_desc
         ds = L.AdamWDesc()
         ctypes.memmove(ctypes.addressof(ds), ctypes.addressof(d), ctypes.sizeof(d))
-        ds.param, ds.grad = ops.addr(self.P32, lo), ops.addr(self.G32, lo)
+        ds.param, ds.grad = ops.addr(self.P32, lo), d.grad + 4 * lo      # the full one's arena: G32 or GACC
         ds.exp_avg, ds.exp_avg_sq = ops.addr(self.M, lo), ops.addr(self.V, lo)
         ds.max_exp_avg_sq, ds.param16 = ops.addr(self.VMAX, lo), ops.addr(self.P16, lo)
         ds.n = hi - lo
@@ -447,7 +454,7 @@ class EngineBase:
         return ds
 
     def _adam_keep(self):
-        return (self.P32, self.G32, self.M, self.V, self.VMAX, self.P16, self.opt_state)
+        return (self.P32, self.G_OPT, self.M, self.V, self.VMAX, self.P16, self.opt_state)
 
     def _adam_call(self, d):
         return ops.Call("vqa_adamw_amsgrad", ctypes.byref(d), desc=d, keep=self._adam_keep())
@@ -654,10 +661,10 @@ class EngineBase:
         return self.LOGP[:self.rows].cpu().numpy(), float(self.LOSS.item())
 
     def grad_norm(self):
-        return float(self.G32.double().norm()) * self.grad_scale
+        return float(self.G_OPT.double().norm()) * self.grad_scale
 
     def group_grad_norms(self):
-        return {g: float(self.G32[a:e].double().norm()) * self.grad_scale for g, (a, e) in self.lay.groups.items()}
+        return {g: float(self.G_OPT[a:e].double().norm()) * self.grad_scale for g, (a, e) in self.lay.groups.items()}
 
     def last_grad_norm(self):
         return float(self.opt_state[L.ST_GRAD_NORM].item())

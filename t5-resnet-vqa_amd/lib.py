@@ -278,6 +278,9 @@ register("vqa_rollout_cls", P, c_int, c_int, c_int, c_ll, c_ll, P, P)
 register("vqa_channel_cam", P, c_int, c_int, c_int, P, P, P)
 register("vqa_upsample2x_nhwc", P, P, c_int, c_int, c_int, c_int)
 register("vqa_optim_finalize", P, c_int, c_float, c_float, c_int, c_int, c_float, c_float, P)
+register("vqa_grad_accumulate", P, P, c_ll, P)
+register("vqa_accum_advance", P, P, c_int, c_int, c_int, P, P, P)
+register("vqa_accum_finish", P, P, P, c_int)
 
 
 def check(rc, what):

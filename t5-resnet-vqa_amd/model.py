@@ -146,6 +146,14 @@ class ResnetVQAModel:
                                 num_blocks=self.num_attention_blocks, language_model=self.language_model_name,
                                 **self._cfg, **opt)
         self._opt = opt
+        self.engine.use_accumulation(getattr(self, "accumulation_steps", 1))    # survives a rebuild
+
+    def use_accumulation(self, k):
+        """k micro-batches of batch_size rows per optimizer step (engine.use_accumulation; the
+        trainer's accumulation_steps): load_items / train_one_step then take up to k x batch_size
+        rows.  Before the first training step."""
+        self.engine.use_accumulation(k)
+        self.accumulation_steps = int(k)
 
     def train(self, mode=True):
         """nn.Module.train: dropout on (the reference trains with p = 0.1 at every site)."""
@@ -157,11 +165,14 @@ class ResnetVQAModel:
         return self.train(False)
 
     # ------------------------------------------------------------------ forward
-    def _check_batch(self, question_input_ids, image_tensors):
+    def _check_batch(self, question_input_ids, image_tensors, accumulate=False):
         n = int(question_input_ids.shape[0])
         lo = 0 if self.engine.allow_empty_rows else 1         # 0: an empty data-parallel rank
-        if not lo <= n <= self.batch_size:
-            raise ValueError(f"batch of {n} rows: the model is planned for {lo}..{self.batch_size} rows")
+        hi = self.batch_size
+        if accumulate:                                        # a global batch of an accumulated step
+            lo, hi = 1, self.engine.accum * self.batch_size
+        if not lo <= n <= hi:
+            raise ValueError(f"batch of {n} rows: the model is planned for {lo}..{hi} rows")
         want_q = (n, self.seq_len)
         want_i = (n, 3, self.image_size, self.image_size)
         if tuple(question_input_ids.shape) != want_q:
@@ -169,8 +180,14 @@ class ResnetVQAModel:
         if tuple(image_tensors.shape) != want_i:
             raise ValueError(f"image_tensors shape {tuple(image_tensors.shape)} != planned {want_i}")
 
-    def load_items(self, items):
-        """The reference collate's batch dict (the keys train_one_step passes on)."""
+    def load_items(self, items, accumulate=False):
+        """The reference collate's batch dict (the keys train_one_step passes on).  accumulate (an
+        accumulated training step only): the dict is a global batch of up to accumulation_steps x
+        batch_size rows; it is checked here and loaded micro-batch by micro-batch by
+        engine.accum_step, which the trainer calls next."""
+        if accumulate:
+            self._check_batch(items["question_input_ids"], items["image_tensors"], accumulate=True)
+            return
         self.load_batch(items["question_input_ids"], items["question_attention_masks"], items["image_tensors"],
                         items.get("annotation_ids"))
 

@@ -33,6 +33,12 @@ own batch and `train_one_step` runs `dp.DataParallelStep` -- the gradient bucket
 all-reduced over RCCL while the backward runs, the embedding rows all-gathered --
 so every rank applies the same update.  The returned loss / log-probs are the
 rank's own (its batch), the clip norm is the global one.
+
+Gradient accumulation (not in the reference): `accumulation_steps=k` makes `train_one_step`
+take a global batch of up to k x batch_size rows and run it as k micro-batches and ONE
+optimizer step (engine.use_accumulation / accum_step); it returns the global batch's loss
+and log-probs, and every count here (num_training_steps, warm-up, the schedule, the
+checkpoints) stays in optimizer steps.  Single GPU, ResnetVQAModel / FasterRcnnVQAModel only.
 """
 from __future__ import annotations
 
@@ -53,7 +59,8 @@ HARD_CODED_LR = 5e-4          # faster_rcnn_vqa_trainer.py:244-261
 class VQATrainer:
     def __init__(self, model: ResnetVQAModel, optimizer_kwargs: dict, lr_scheduler_kwargs: dict,
                  num_training_steps: int, gradient_clipping=1.0, use_graph=True, logger=print,
-                 data_parallel=None, process_group=None, bucket_mb=24, shard_optimizer=False):
+                 data_parallel=None, process_group=None, bucket_mb=24, shard_optimizer=False,
+                 accumulation_steps=1):
         if optimizer_kwargs.get("type", "AdamW") != "AdamW":
             raise ValueError("only AdamW is on this path (vit_daquar_config.json:41)")
         kw = dict(optimizer_kwargs.get("kwargs", {}))
@@ -65,6 +72,20 @@ class VQATrainer:
             data_parallel = (torch.distributed.is_available() and torch.distributed.is_initialized()
                              and torch.distributed.get_world_size(process_group) > 1)
         self.data_parallel = bool(data_parallel)
+        # accumulation_steps = k > 1: train_one_step takes a global batch of up to k x batch_size rows
+        # and runs it as k micro-batches and ONE optimizer step (engine.use_accumulation); steps,
+        # warm-up, the schedule and the checkpoints keep counting optimizer steps
+        self.accumulation_steps = int(accumulation_steps)
+        if self.accumulation_steps < 1:
+            raise ValueError(f"accumulation_steps={accumulation_steps} must be >= 1")
+        if self.accumulation_steps > 1 and self.data_parallel:
+            raise ValueError("accumulation_steps > 1 together with data parallel (skipping the exchange on "
+                             "non-final micro-batches) is not planned")
+        if self.accumulation_steps > 1 and not hasattr(model, "use_accumulation"):
+            raise ValueError("accumulation_steps > 1 is planned for ResnetVQAModel; the ViT model's engine does not "
+                             "accumulate")
+        if self.accumulation_steps > 1:
+            model.use_accumulation(self.accumulation_steps)
         if self.data_parallel and not hasattr(model.engine, "ready_marks"):
             raise ValueError("data parallel training is planned for ResnetVQAModel (BASELINE configs[2]); "
                              "the ViT configuration (configs[3]) is a single-GPU one")
@@ -108,8 +129,12 @@ class VQATrainer:
         m = self.model
         if not m.training:
             m.train()
-        m.load_items(data_items)
         e = m.engine
+        if self.accumulation_steps > 1:
+            m.load_items(data_items, accumulate=True)       # checked here, loaded per micro-batch
+            e.accum_step(data_items, use_graph=self.use_graph)
+            return (float(e.LOSS.item()) if sync else e.LOSS[0]), e.accum_log_probs()
+        m.load_items(data_items)
         if self.data_parallel:
             if self._dp is None:
                 self._dp = dp.DataParallelStep(e, group=self.process_group, bucket_mb=self.bucket_mb,
