@@ -343,10 +343,7 @@ class DataParallelStep:
                 sq.append(ops.Call("vqa_grad_sqnorm", ops.addr(e.G32, lo), hi - lo, ops.addr(self.WS_SQN, i * K), K,
                                    keep=(e.G32, self.WS_SQN)))
         self.sq_calls = sq
-        fin = []
-        e._call(fin, "vqa_optim_finalize", self.WS_SQN, len(ranges) * K, float(e.grad_scale), float(e.max_norm),
-                int(e.warmup), int(e.total), float(e.betas[0]), float(e.betas[1]), e.opt_state)
-        self.finalize_call = fin[0]
+        self.finalize_call = e._finalize_call(self.WS_SQN, len(ranges) * K)
         self.adam_calls = [e.adam_range_call(lo, hi) for lo, hi in ranges]
         # reduce-scatter outputs, one slice per bucket (several are in flight at once); each is
         # copied into the rank's chunk of G32 once its collective is done
@@ -472,34 +469,28 @@ class DataParallelStep:
         # behind the early buckets' collectives: at world 1 they did not overlap anything (trace), and at
         # N > 1 that stream's wait on a running collective would hold back whatever stage kernels share
         # its hardware queue
-        # the embedding table's update split by rows (engine.emb_pre; bit-identical to the dense
+        # the embedding table's update split by rows (engine.StepTail; bit-identical to the dense
         # range): the rows no rank touched beside the first stage (marks from the gathered ids),
         # the rel-bias range and the touched rows in the finish graph.  The squared-norm partials of
         # [0, a) (engine._sq_split) run on the comm stream right behind the all-reduce that completes
-        # that prefix, so the finish keeps only the later partials.
+        # that prefix (_sq0_stage), and the finish then keeps only the later partials: one decision,
+        # _sq0_comm, which _backward_exchange tests where it issues them.
+        t = e.tail
         self.emb_pre = []
         self._sq0_stage = None
-        opt = list(e.opt_calls)
         if not self.shard:
             if e.embed_split:
-                self.emb_pre = [ops.Call("vqa_embed_mark", self.GIDS.data_ptr(), self.world * e.T, S.T5_VOCAB,
-                                         e.EMB_MARK.data_ptr(), e.opt_state.data_ptr(),
-                                         keep=(self.GIDS, e.EMB_MARK, e.opt_state)), e.emb_pre[1]]
+                self.emb_pre = [e.embed_mark_call(self.GIDS, self.world * e.T), t.rows_rest]
                 self.stages[0]["ops"].insert(0, ("emb", self.emb_pre))
-                opt = opt[:2] + list(e.tail_calls_unfused)
-            a = e._sq_split[1] if e._sq_split is not None else None
-            if a is not None:
-                done = 0
-                for j, st in enumerate(self.stages):
-                    if st["final"]:
-                        done = max(done, max(self.buckets[k][2] for k in st["final"]))
-                    if done >= a and st["final"]:
+            done = 0
+            for j, st in enumerate(self.stages if e._sq_split is not None else ()):
+                if st["final"]:
+                    done = max(done, max(self.buckets[k][2] for k in st["final"]))
+                    if done >= e._sq_split[1]:
                         self._sq0_stage = j
                         break
-            if self._sq0_stage is not None:
-                assert opt[0].name == "vqa_grad_sqnorm"
-                self._sq0_call = opt[0]
-                opt = opt[1:]
+        self._sq0_comm = self._sq0_stage is not None and (COMM_ON_STREAM or _staged(e.G32, self.group))
+        opt = ([] if self._sq0_comm else [t.sq_a]) + [t.sq_b] + t.split
         self.finish_calls = self.tail + [self.emb_call] + ([] if self.shard else opt)
         # (high-priority streams -- hardware queues of their own -- measured 2.5x slower, r04)
         # issues the collectives behind the stage events (VQA_DP_COMM, an A/B switch: "own" a stream of
@@ -583,8 +574,8 @@ class DataParallelStep:
                     for k in ks:
                         works[k] = ws if k == ks[-1] else []
                         mark_done(k, ws)
-                    if j == self._sq0_stage and (COMM_ON_STREAM or _staged(e.G32, self.group)):
-                        self._sq0_call(L.stream_handle(comm))     # behind the all-reduce of [0, a)
+                    if self._sq0_comm and j == self._sq0_stage:
+                        e.tail.sq_a(L.stream_handle(comm))        # behind the all-reduce of [0, a)
         if tm is not None:
             tm["wait"] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             tm["wait"][0].record(main)

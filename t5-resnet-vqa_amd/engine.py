@@ -79,6 +79,45 @@ def accum_spans(rows, batch, k):
     return [(min(j * batch, rows), min((j + 1) * batch, rows)) for j in range(k)]
 
 
+class StepTail:
+    """The calls of the step's tail, each planned once (VQAEngine._plan_optimizer) and taken by
+    name; the three forms the steps run are lists of these names.
+      sq_a, sq_b, sq_c   vqa_grad_sqnorm partials of [0, a), [a, rel-bias) and [rel-bias, n)
+      finalize           vqa_optim_finalize over the three
+      after              what follows finalize in the dense form: the whole AdamW pass and the e4m3
+                         copies, or with a deferred update the [rel-bias, n) range
+      mark, rows_rest    embed_split: vqa_embed_mark of the step's ids; the untouched rows (grid 256)
+      relbias, rows_touched          ... the rel-bias-only range; the touched rows (grid 1)
+      sort, scatter      fused_tail: the embedding scatter's id sort; the scatter over the sorted ids
+      sq_final           ... vqa_grad_sqnorm_final: sq_b + sq_c + finalize in one launch"""
+    mark = rows_rest = relbias = rows_touched = sort = scatter = sq_final = None
+
+    def __init__(self, sq_a, sq_b, sq_c, finalize):
+        self.sq_a, self.sq_b, self.sq_c, self.finalize = sq_a, sq_b, sq_c, finalize
+        self.after = []
+
+    @property
+    def dense(self):
+        """opt_calls: eager steps."""
+        return [self.sq_a, self.sq_b, self.sq_c, self.finalize] + self.after
+
+    @property
+    def split(self):
+        """tail_calls_unfused: what follows sq_a and sq_b when the untouched rows ran earlier
+        (dp.DataParallelStep's and the accumulated step's finish graphs); without the row split
+        the rest of the dense form."""
+        if self.rows_touched is None:
+            return [self.sq_c, self.finalize] + self.after
+        return [self.sq_c, self.finalize, self.relbias, self.rows_touched]
+
+    @property
+    def short(self):
+        """tail_calls: what the stream / graph step runs after run_backward_streams."""
+        if self.sq_final is None:
+            return self.split
+        return [self.sq_final, self.relbias, self.rows_touched]
+
+
 class VQAEngine(EngineBase):
     def __init__(self, state_dict, vision="resnet50", batch=64, seq_len=32, image_size=224, device="cuda:0",
                  warmup=10, total=100, num_blocks=3, answer_spaces=170, grad_scale=1.0, max_norm=1.0,
@@ -604,26 +643,27 @@ class VQAEngine(EngineBase):
                              slot=self.nl - 1 - i_hi)
 
     # ------------------------------------------------------------------ optimizer plan
+    def embed_mark_call(self, ids, rows):
+        """vqa_embed_mark of `rows` token ids: EMB_MARK[id] = the step counter (the engine's own ids;
+        dp.DataParallelStep: every rank's, gathered)."""
+        return ops.Call("vqa_embed_mark", ids.data_ptr(), rows, S.T5_VOCAB, self.EMB_MARK.data_ptr(),
+                        self.opt_state.data_ptr(), keep=(ids, self.EMB_MARK, self.opt_state))
+
     def _plan_optimizer(self):
-        o = self.opt_calls
+        """Plans every call of the step's tail once, under a name on self.tail (StepTail, DESIGN
+        §3.7 "step tail"), and sets the lists the steps run from its compositions."""
         n = self.lay.total
-        # squared-norm partials over two ranges: [0, rel-bias) is final once the backward's
-        # deferred column sums are flushed, so graph steps run it beside the embedding-gradient
-        # scatter (run_backward_streams); the rel-bias + embedding-table range follows it
-        # [0, a) is final once the first T5 weight-gradient group is (graph steps run that part
-        # beside the backward's last layers), [a, rel-bias) with the last group
+        # squared-norm partials: [0, a) is final once the first T5 weight-gradient group is (graph
+        # steps run that part beside the backward's last layers), [a, rel-bias) once the deferred
+        # column sums are flushed, the rel-bias + embedding-table range after the scatter
         e0 = self.lay["t5.relbias"].offset
         a = self._sq_split[1] if self._sq_split is not None else e0
         assert a % 4 == 0 and e0 % 4 == 0 and (n - e0) % 4 == 0 and a <= e0
         K = self.SQ_PARTS
         G = self.G_OPT                    # G32, or the accumulator (use_accumulation)
-        self._call(o, "vqa_grad_sqnorm", G, a, self.WS_SQ, K)
-        self._call(o, "vqa_grad_sqnorm", ops.addr(G, a), e0 - a, ops.addr(self.WS_SQ, K), K,
-                   extra=[G, self.WS_SQ])
-        self._call(o, "vqa_grad_sqnorm", ops.addr(G, e0), n - e0, ops.addr(self.WS_SQ, 2 * K), K,
-                   extra=[G, self.WS_SQ])
-        self._call(o, "vqa_optim_finalize", self.WS_SQ, 3 * K, float(self.grad_scale), float(self.max_norm),
-                   int(self.warmup), int(self.total), float(self.betas[0]), float(self.betas[1]), self.opt_state)
+        sq = [ops.Call("vqa_grad_sqnorm", ops.addr(G, lo), hi - lo, ops.addr(self.WS_SQ, i * K), K,
+                       keep=(G, self.WS_SQ)) for i, (lo, hi) in enumerate(((0, a), (a, e0), (e0, n)))]
+        self.tail = t = StepTail(*sq, self._finalize_call(self.WS_SQ, 3 * K))
         self._adam_desc = self._adam_desc_full()
         self.adam_full = self._adam_call(self._adam_desc)
         # Deferred update (defer_opt): step k's AdamW runs inside step k+1's forward, one
@@ -635,10 +675,10 @@ class VQAEngine(EngineBase):
         # (With fuse_norm a T5 layer's wo GEMM reads the next layer's ln0 gain, so the layer
         # also waits for the next layer's range: _t5_waits.)
         lay = self.lay
-        cuts = [("embed", lay["t5.relbias"].offset, n)]
+        cuts = [("embed", e0, n)]
         for i in range(self.nl):
             lo = lay[f"t5.{i}.qkv_w"].offset if i < self.nl - 1 else lay["t5.final_ln"].offset
-            hi = lay[f"t5.{i - 1}.qkv_w"].offset if i > 0 else lay["t5.relbias"].offset
+            hi = lay[f"t5.{i - 1}.qkv_w"].offset if i > 0 else e0
             cuts.append((f"t5.{i}", lo, hi))
         cuts.append(("scaler", lay["scaler_w"].offset, lay["t5.final_ln"].offset))
         cuts.append(("head", 0, lay["scaler_w"].offset))     # classifier, pooler, SGA
@@ -658,7 +698,6 @@ class VQAEngine(EngineBase):
                 self._quant_weight(quant[nm], wname, rows)
                 self.quant_all += quant[nm][-1:]
         self.adam_segs = []
-        self.adam_embed = None
         for name, lo, hi in cuts:
             c = self.adam_range_call(lo, hi)
             if quant[name]:
@@ -667,26 +706,17 @@ class VQAEngine(EngineBase):
                 self.adam_embed = c
             else:
                 self.adam_segs.append((name, c))
-        lst = []
-        self._call(lst, "vqa_zero", ops.addr(self.opt_state, L.ST_PENDING), 16, extra=[self.opt_state])
-        self.clear_pending = lst[0]
-        if not self.defer_opt:
-            o.append(self.adam_full)
-            o += self.quant_all
-        elif self.adam_embed is not None:
-            o.append(self.adam_embed)
+        self.clear_pending = ops.Call("vqa_zero", ops.addr(self.opt_state, L.ST_PENDING), 16, keep=(self.opt_state,))
+        t.after = [self.adam_embed] if self.defer_opt else [self.adam_full] + self.quant_all
         # The embedding table's update split by rows (vqa_adamw_rows): the rows no
         # token of the step touched have a zero gradient, so their update runs beside the
-        # backward (emb_pre: mark the step's ids, then those rows), and the step's exposed tail
-        # keeps only the rel-bias range and the touched rows (tail_calls).  Bit-identical to the
-        # dense range; used by the stream / graph step (run_backward_streams with sq_overlap),
-        # while opt_calls keeps the dense form (eager steps, dp.DataParallelStep's finish graph).
+        # backward (mark the step's ids, then those rows), and the step's exposed tail keeps
+        # only the rel-bias range and the touched rows.  Bit-identical to the dense range.
         self.embed_split = self.defer_opt
-        self.tail_calls = o[2:]
-        self.emb_pre = []
+        T, emb = self.T, lay["t5.embed"]
+        self.fused_tail = self.embed_split and T <= 16384          # one sort slice
         if self.embed_split:
-            emb = lay["t5.embed"]
-            assert emb.offset + emb.numel == n and self.adam_embed is o[-1]
+            assert emb.offset + emb.numel == n
             if self.EMB_MARK is None:
                 self.EMB_MARK = torch.full((S.T5_VOCAB,), -1, dtype=torch.int32, device=self.dev)
             lo = emb.offset
@@ -695,45 +725,33 @@ class VQAEngine(EngineBase):
             rows_call = lambda touched: ops.Call("vqa_adamw_rows", ctypes.byref(dt), self.EMB_MARK.data_ptr(),  # noqa: E731
                                                  S.T5_VOCAB, self.D, touched, int(self.warmup), int(self.total),
                                                  desc=dt, keep=keep)
-            self.emb_pre = [ops.Call("vqa_embed_mark", self.IDS.data_ptr(), self.T, S.T5_VOCAB,
-                                     self.EMB_MARK.data_ptr(), self.opt_state.data_ptr(),
-                                     keep=(self.IDS, self.EMB_MARK, self.opt_state)),
-                            # the untouched rows' pass as 256 workgroups striding over the rows: a
-                            # 32k-block grid beside the chain cost what it saved at the tail (A/B:
-                            # 6.47-6.48 ms either way), 256 measured 6.44-6.47
-                            rows_call(256)]
-            self.tail_calls = o[2:-1] + [self.adam_range_call(lay["t5.relbias"].offset, lo), rows_call(1)]
-        # The graph / stream step's shorter tail ("step tail"; needs the row marks):
-        #  * the embedding scatter's id sort runs beside the T5 backward (emb_sort_call; it reads IDS
-        #    alone and nothing else writes WS_EMB), the chain's end keeps the scatter (emb_scatter_call);
-        #  * ONE launch sums the ranges [a, rel-bias) and [rel-bias, n) and finalizes
-        #    (vqa_grad_sqnorm_final); of the table it loads the marked rows only -- every other
-        #    row is exactly zero (vqa_embedding_zero_rows), so the partials are the dense ones.
-        # tail_calls is what that step runs after run_backward_streams; tail_calls_unfused keeps
-        # sqnorm + finalize + the two AdamW parts (dp.DataParallelStep's finish graph, whose
-        # scatter and marks come from the gathered ids).
-        self.tail_calls_unfused = self.tail_calls
-        T = self.T
-        self.fused_tail = self.embed_split and T <= 16384          # one sort slice
-        self.emb_sort_call = self.emb_scatter_call = None
+            t.mark = self.embed_mark_call(self.IDS, T)
+            # the untouched rows' pass as 256 workgroups striding over the rows: a 32k-block grid
+            # beside the chain cost what it saved at the tail (A/B: 6.47-6.48 ms either way), 256
+            # measured 6.44-6.47
+            t.rows_rest = rows_call(256)
+            t.relbias, t.rows_touched = self.adam_range_call(e0, lo), rows_call(1)
+        # The graph / stream step's shorter tail (needs the row marks): the scatter's id sort can run
+        # beside the T5 backward (it reads IDS alone and nothing else writes WS_EMB), and ONE launch
+        # sums [a, rel-bias) and [rel-bias, n) and finalizes; of the table it loads the marked rows
+        # only -- every other row is exactly zero (vqa_embedding_zero_rows): the dense partials.
         if self.fused_tail:
             if self.SQ_CNT is None:
                 self.SQ_CNT = torch.zeros(L.SQNORM_FINAL_COUNTER_WORDS, dtype=torch.int32,
                                           device=self.dev)        # arrival counters, left at zero
-            emb = lay["t5.embed"]
             lead = emb.offset - e0
             assert lead >= 0 and lead % 4 == 0 and emb.numel == S.T5_VOCAB * self.D and self.D % 4 == 0
-            fin = ops.Call("vqa_grad_sqnorm_final", ops.addr(G, a), e0 - a, ops.addr(G, e0), n - e0,
-                           self.WS_SQ.data_ptr(), K, 3 * K, self.EMB_MARK.data_ptr(), lead, self.D,
-                           self.SQ_CNT.data_ptr(), float(self.grad_scale), float(self.max_norm), int(self.warmup),
-                           int(self.total), float(self.betas[0]), float(self.betas[1]), self.opt_state.data_ptr(),
-                           keep=(G[a:], self.WS_SQ, self.EMB_MARK, self.SQ_CNT, self.opt_state))
-            assert [c.name for c in self.tail_calls[:2]] == ["vqa_grad_sqnorm", "vqa_optim_finalize"]
-            self.tail_calls = [fin] + self.tail_calls[2:]
-            ids, dh, dtab, _, _, _, ws = self.emb_call.args
-            self.emb_sort_call = ops.Call("vqa_embedding_sort", ids, T, S.T5_VOCAB, ws, keep=(self.IDS, self.WS_EMB))
-            self.emb_scatter_call = ops.Call("vqa_embedding_bwd_sorted", dh, dtab, T, self.D, S.T5_VOCAB, ws,
-                                             keep=(self.dH32, self.G32, self.WS_EMB))
+            t.sq_final = ops.Call("vqa_grad_sqnorm_final", ops.addr(G, a), e0 - a, ops.addr(G, e0), n - e0,
+                                  self.WS_SQ.data_ptr(), K, 3 * K, self.EMB_MARK.data_ptr(), lead, self.D,
+                                  self.SQ_CNT.data_ptr(), *self._optim_scalars(), self.opt_state.data_ptr(),
+                                  keep=(G[a:], self.WS_SQ, self.EMB_MARK, self.SQ_CNT, self.opt_state))
+            ids, ws = self.IDS.data_ptr(), self.WS_EMB.data_ptr()
+            t.sort = ops.Call("vqa_embedding_sort", ids, T, S.T5_VOCAB, ws, keep=(self.IDS, self.WS_EMB))
+            t.scatter = ops.Call("vqa_embedding_bwd_sorted", self.dH32.data_ptr(), self.g32["t5.embed"].data_ptr(), T,
+                                 self.D, S.T5_VOCAB, ws, keep=(self.dH32, self.G32, self.WS_EMB))
+        self.opt_calls, self.tail_calls_unfused, self.tail_calls = t.dense, t.split, t.short
+        self.emb_pre = [t.mark, t.rows_rest] if self.embed_split else []
+        self.emb_sort_call, self.emb_scatter_call = t.sort, t.scatter
 
     def _adam_groups(self):
         ends, lrs = self.lay.group_of_element()
@@ -747,9 +765,7 @@ class VQAEngine(EngineBase):
     def set_grad_scale(self, s):
         """DP: grads are summed over ranks; the average enters as a scale."""
         self.grad_scale = float(s)
-        self.opt_calls = []
-        self._plan_optimizer()
-        self.graph = None
+        self._replan_optimizer()
 
     # ------------------------------------------------------------------ execution
     def load_batch(self, batch, next_images=None):
@@ -873,12 +889,13 @@ class VQAEngine(EngineBase):
         self.set_grad_scale(self.grad_scale / k)          # re-plans over GACC (G_OPT), drops the graph
 
     def _finish_calls(self):
-        """The finish graph of an accumulated step, the dense tail over GACC in the shape of
-        tail_calls_unfused: the untouched table rows (before finalize; the marks are the union of
-        the k micro-batches', all stamped with the one step counter), the squared-norm partials,
-        finalize, the rel-bias range and the touched rows -- without defer_optimizer the whole
-        AdamW pass -- then vqa_accum_finish."""
-        return self.emb_pre[1:] + self.opt_calls[:2] + self.tail_calls_unfused + [self.accum_finish]
+        """The finish graph of an accumulated step, the tail over GACC: the untouched table rows
+        (before finalize; the marks are the union of the k micro-batches', all stamped with the one
+        step counter), the squared-norm partials, finalize, the rel-bias range and the touched rows
+        -- without defer_optimizer the whole AdamW pass -- then vqa_accum_finish."""
+        t = self.tail
+        rest = [t.rows_rest] if self.embed_split else []
+        return rest + [t.sq_a, t.sq_b] + t.split + [self.accum_finish]
 
     def _micro_backward(self):
         """A micro-batch's backward: no tail.  The untouched-rows pass and the squared-norm overlap
@@ -888,7 +905,7 @@ class VQAEngine(EngineBase):
         on the main stream by this micro-batch's forward: the accumulate, which overwrites GACC in
         micro-batch 0, follows all of them in stream order."""
         if self.embed_split:
-            self._run(self.emb_pre[:1])
+            self._run([self.tail.mark])
         self.run_backward_streams()
         self._run(self.accum_calls)
 
@@ -939,17 +956,14 @@ class VQAEngine(EngineBase):
         self.flush_optimizer()                          # the previous step's deferred update, then the forward
         super().forward()
 
-    def _run_step_streams(self, optimizer=True):
+    def _run_step_streams(self):
         """One step with graph-level concurrency: the frozen-ResNet + ConvTranspose2d
         branch and the T5 encoder run on two streams in the forward (they meet at
         SGA block 0), and the scaler weight gradient overlaps the T5 backward.
         Buffers of the two branches are disjoint, so the result is the same as
         the sequential order (and bit-identical: no cross-branch reductions)."""
         self.run_forward_streams()
-        if optimizer:
-            self._backward_and_tail()
-        else:
-            self.run_backward_streams()
+        self._backward_and_tail()
 
     def _backward_and_tail(self):
         """The backward and optimizer tail of a full stream / graph step (an accumulating engine:
@@ -957,7 +971,7 @@ class VQAEngine(EngineBase):
         if self.accum > 1:
             self._micro_backward()
             return
-        self.run_backward_streams(sq_overlap=True, sorted_scatter=self.fused_tail)
+        self.run_backward_streams(sq_overlap=True)
         self._run(self.tail_calls)
 
     def run_forward_streams(self):
@@ -1071,17 +1085,17 @@ class VQAEngine(EngineBase):
         self.clear_pending(hm)                             # the update is applied: once only
         assert set(ev) == set(order)
 
-    def run_backward_streams(self, sq_overlap=False, sorted_scatter=False):
-        """sq_overlap: also run the optimizer plan's first two calls (the squared-norm partials
-        of [0, a), final once the first T5 weight-gradient group is, and of [a, rel-bias),
-        final before the embedding scatter) on `side`, beside the backward's tail; the caller
-        then runs tail_calls (opt_calls[2:], the embedding table's dense update split by rows:
-        emb_pre runs here, on `side`).
-        sorted_scatter (the fused tail): the embedding scatter's id sort runs here on `side`, ahead of
-        emb_pre and beside the T5 backward (it reads IDS alone), and the [a, rel-bias) partials are
-        left to the caller's tail_calls (vqa_grad_sqnorm_final) -- the scatter is then the only
-        launch issued behind the chain, beside the trailing weight-gradient GEMMs on `wside`."""
-        assert sq_overlap or not sorted_scatter
+    def run_backward_streams(self, sq_overlap=False):
+        """sq_overlap (a full step): also run the tail's early parts beside the backward, on `side`:
+        the untouched embedding rows' update (emb_pre), the squared-norm partials of [0, a), final
+        once the first T5 weight-gradient group is, and of [a, rel-bias), final before the embedding
+        scatter; the caller then runs tail_calls.
+        With fused_tail the embedding scatter's id sort also runs here on `side`, ahead of emb_pre
+        and beside the T5 backward (it reads IDS alone), and the [a, rel-bias) partials are left to
+        the caller's tail_calls (vqa_grad_sqnorm_final) -- the scatter is then the only launch
+        issued behind the chain, beside the trailing weight-gradient GEMMs on `wside`."""
+        t = self.tail
+        fused = sq_overlap and self.fused_tail
         main = torch.cuda.current_stream(self.dev)
         side, wside = self._side, self._wside
         b = self.bwd_calls
@@ -1090,12 +1104,12 @@ class VQAEngine(EngineBase):
         _after(side, main)
         with torch.cuda.stream(side):
             self._run(b[q0:q1])                            # scaler dW / db
-            if sorted_scatter:
-                self.emb_sort_call(L.stream_handle(side))
+            if fused:
+                t.sort(L.stream_handle(side))
                 sorted_ev = torch.cuda.Event()
                 sorted_ev.record(side)
-            if sq_overlap:                                 # a full step: the untouched embedding rows'
-                self._run(self.emb_pre)                    # update, beside the T5 backward
+            if sq_overlap:
+                self._run(self.emb_pre)
         if sq_overlap:
             assert b[-1] is self.emb_call
 
@@ -1104,23 +1118,21 @@ class VQAEngine(EngineBase):
                     _after(side, st)
                 with torch.cuda.stream(side):
                     self._run(calls)
+            late = [] if fused else [t.sq_b]
             m1 = self._sq_split[0] if self._sq_split is not None else None
             if m1 is not None and q1 < m1 < len(b) - 1:
                 self._run_tagged(b[q1:m1], main, wside)    # T5 backward up to the first dW group
-                to_side(self.opt_calls[:1])                # grad-norm partials of [0, a), beside the rest
+                to_side([t.sq_a])                          # beside the rest
                 self._run_tagged(b[m1:-1], main, wside)
-                if sorted_scatter:
-                    main.wait_event(sorted_ev)
-                    self._run([self.emb_scatter_call])
-                else:
-                    to_side(self.opt_calls[1:2])           # ... and of [a, rel-bias)
             else:
                 self._run_tagged(b[q1:-1], main, wside)    # T5 backward (+ deferred column sums)
-                if sorted_scatter:
-                    main.wait_event(sorted_ev)
-                    self._run([self.emb_scatter_call])
-                to_side(self.opt_calls[:1] if sorted_scatter else self.opt_calls[:2])
-            if not sorted_scatter:
+                late = [t.sq_a] + late
+            if fused:
+                main.wait_event(sorted_ev)
+                self._run([t.scatter])
+            if late:
+                to_side(late)
+            if not fused:
                 self._run(b[-1:])                          # embedding rows
         else:
             self._run_tagged(b[q1:], main, wside)          # T5 backward + embedding
@@ -1289,20 +1301,7 @@ class VQAEngine(EngineBase):
         self.graph = parts
 
     def _capture_parts(self, s):
-        if self.accum > 1:
-            # graph(micro-batch) x k -> graph(finish): the device counter lets one micro-batch
-            # graph serve every position.  Capture runs neither: GACC and ACC stay as they are
-            # (the warm-up above is a forward and a backward, no accumulate, no advance)
-            assert self.allreduce is None and not self.res_external
-            gm, gf = self._new_graph(), self._new_graph()
-            with torch.cuda.graph(gm, stream=s):
-                if self.pipeline:
-                    self._step_pipelined()
-                else:
-                    self._run_step_streams()
-            with torch.cuda.graph(gf, stream=s):
-                self._run(self._finish_calls())
-            return [gm, gf]
+        assert self.accum == 1 or (self.allreduce is None and not self.res_external)
         if self.allreduce is None:
             g = self._new_graph()
             with torch.cuda.graph(g, stream=s):
@@ -1311,6 +1310,13 @@ class VQAEngine(EngineBase):
                 else:
                     self._run_step_streams()
             parts = [g]
+            if self.accum > 1:
+                # graph(micro-batch) x k -> graph(finish): the device counter lets one micro-batch
+                # graph serve every position.  Capture runs neither: GACC and ACC stay as they are
+                # (the warm-up above is a forward and a backward, no accumulate, no advance)
+                parts.append(self._new_graph())
+                with torch.cuda.graph(parts[1], stream=s):
+                    self._run(self._finish_calls())
         else:
             g1, g2 = self._new_graph(), self._new_graph()
             with torch.cuda.graph(g1, stream=s):

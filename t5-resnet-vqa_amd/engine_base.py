@@ -481,9 +481,25 @@ class EngineBase:
             self.betas = tuple(betas)
         if eps is not None:
             self.eps = float(eps)
+        self._replan_optimizer()
+
+    def _replan_optimizer(self):
+        """Plan the optimizer tail again from the current settings; a captured step graph holds
+        the old calls and is dropped."""
         self.opt_calls = []
         self._plan_optimizer()
         self.graph = None
+
+    def _optim_scalars(self):
+        """The clip and schedule scalars of vqa_optim_finalize (and vqa_grad_sqnorm_final), in
+        argument order."""
+        return (float(self.grad_scale), float(self.max_norm), int(self.warmup), int(self.total),
+                float(self.betas[0]), float(self.betas[1]))
+
+    def _finalize_call(self, ws, parts):
+        """vqa_optim_finalize over the `parts` squared-norm partials in `ws`."""
+        return ops.Call("vqa_optim_finalize", ops.addr(ws), parts, *self._optim_scalars(), ops.addr(self.opt_state),
+                        keep=(ws, self.opt_state))
 
     # ------------------------------------------------------------------ execution
     def set_training(self, mode=True):

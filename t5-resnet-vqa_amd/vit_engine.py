@@ -314,8 +314,7 @@ class VitVQAEngine(EngineBase):
         o = self.opt_calls
         n = self.lay.total
         self._call(o, "vqa_grad_sqnorm", self.G32, n, self.WS_SQ, self.SQ_PARTS)
-        self._call(o, "vqa_optim_finalize", self.WS_SQ, self.SQ_PARTS, float(self.grad_scale), float(self.max_norm),
-                   int(self.warmup), int(self.total), float(self.betas[0]), float(self.betas[1]), self.opt_state)
+        o.append(self._finalize_call(self.WS_SQ, self.SQ_PARTS))
         self._adam_desc = self._adam_desc_full()
         # AdamW at the end of the step (a no-op unless the finalize flagged a pending update).
         # Deferring it into the next step beside the frozen ViT, which reads no trained

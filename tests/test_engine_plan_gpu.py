@@ -55,6 +55,37 @@ def test_plan_ignores_retired_switches_and_stem_follows_the_image_size(pkg, monk
     assert tuple(eng.IMG8.shape) == (2, 41, 41, 16)
 
 
+@pytest.mark.gpu
+def test_tail_lists_are_the_named_compositions(pkg):
+    """opt_calls, tail_calls_unfused, tail_calls and emb_pre are the tail's named calls
+    (engine.StepTail) in the documented order, the very objects: with the deferred update the row
+    split and the fused tail, without it the whole AdamW pass after finalize and nothing split."""
+    sd = pkg.synthetic.make_state_dict("resnet50", seed=0)
+
+    def build(**kw):
+        eng = pkg.engine.VQAEngine(sd, vision="resnet50", batch=2, seq_len=16, image_size=64, **kw)
+        t = eng.tail
+        assert [c.name for c in (t.sq_a, t.sq_b, t.sq_c, t.finalize)] == ["vqa_grad_sqnorm"] * 3 + ["vqa_optim_finalize"]
+        assert eng.opt_calls == t.dense and eng.tail_calls_unfused == t.split and eng.tail_calls == t.short
+        return eng, t
+    eng, t = build()
+    assert eng.embed_split and eng.fused_tail
+    assert eng.opt_calls == [t.sq_a, t.sq_b, t.sq_c, t.finalize, eng.adam_embed]
+    assert eng.tail_calls_unfused == [t.sq_c, t.finalize, t.relbias, t.rows_touched]
+    assert eng.tail_calls == [t.sq_final, t.relbias, t.rows_touched]
+    assert eng.emb_pre == [t.mark, t.rows_rest] and (eng.emb_sort_call, eng.emb_scatter_call) == (t.sort, t.scatter)
+    assert [c.name for c in eng.tail_calls + eng.emb_pre + [t.sort, t.scatter]] == [
+        "vqa_grad_sqnorm_final", "vqa_adamw_amsgrad", "vqa_adamw_rows", "vqa_embed_mark", "vqa_adamw_rows",
+        "vqa_embedding_sort", "vqa_embedding_bwd_sorted"]
+    assert (t.rows_rest.args[4], t.rows_touched.args[4]) == (256, 1)
+    eng, t = build(defer_optimizer=False)
+    assert not eng.embed_split and not eng.fused_tail
+    assert eng.opt_calls == [t.sq_a, t.sq_b, t.sq_c, t.finalize, eng.adam_full] + eng.quant_all
+    assert eng.tail_calls == eng.tail_calls_unfused == [t.sq_c, t.finalize, eng.adam_full] + eng.quant_all
+    assert eng.emb_pre == [] and eng.emb_sort_call is None and eng.emb_scatter_call is None
+    assert (t.mark, t.rows_rest, t.relbias, t.rows_touched, t.sort, t.scatter, t.sq_final) == (None,) * 7
+
+
 PLANS = {"defaults": {}, "fuse_norm": dict(fuse_norm=True), "fp8": dict(fp8=True),
          "fp8_fuse_norm": dict(fp8=True, fuse_norm=True), "paired_dw": dict(t5_dw_group=1, sga_dw_batch=False),
          "sga_attn_group_off": dict(sga_attn_group=False), "blocks_1": dict(num_blocks=1),

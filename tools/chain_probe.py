@@ -50,8 +50,7 @@ tiny = torch.zeros(1, device=dev)
 
 def chain():
     eng.run_forward_streams()
-    eng.run_backward_streams(sq_overlap=True)
-    eng._run(eng.opt_calls[2:])
+    eng._backward_and_tail()
 
 
 def forked(body, s):
